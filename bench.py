@@ -23,8 +23,17 @@ radius 200 m), and `--config 3` one GPU's uuid shard of config 3 (100 x 100 km
 metro graph, 125k vehicles x 100 probes = 12.5M points per GPU): secondary
 lines, not the headline.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line:
+`value` and `ms_per_step` with the run's configuration.  `--full` adds what
+takes runs of its own: the per-kernel times and the roofline, the
+host-inclusive, JSON and config-5 stream legs, the oracle check and the CPU
+baselines (null in a plain run's line).  `--dump-outputs DIR` writes what the
+last timed step returned as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  Run:
-  python bench.py                      # N=1, defaults
+  python bench.py                      # N=1, the headline figure alone
+  python bench.py --full               # every leg, check and baseline
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 import argparse
@@ -131,7 +140,46 @@ def parse():
                          "16 measured 5.5-6.0M records/s against 4.7-4.8M at 8, profiles/r06/sthr/)")
     ap.add_argument("--stream-cpu-vehicles", type=int, default=200,
                     help="config-5 CPU baseline / oracle check: vehicles of the stream replayed record at a time")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-kernel times and roofline, the host-inclusive, JSON and "
+                         "config-5 stream legs, the oracle check and the CPU baselines (each still has its own "
+                         "switch above); without it the run only sets up, warms up, times --steps steps and prints "
+                         "the line with those blocks null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to DIR/<name>.npy (float64): "
+                         "traces, segments, reports, way_ids (the batch's typed records, one column per field) and "
+                         "hist, speed_sum (the window's per-segment histogram); rank 0's")
+    args = ap.parse_args()
+    if not args.full:
+        args.host_steps = args.json_calls = args.stream_runs = 0
+        args.no_cpu_baseline = args.no_check = True
+    return args
+
+
+DUMP_BYTES_PER_ARRAY = 8 << 20  # six arrays: 48 MB at the most
+
+
+def dump_outputs(path, res, hist, speed_sum):
+    """The timed path's outputs as float64 .npy files under `path`.  A record
+    array becomes [rows, fields] (padding left out); an array above
+    DUMP_BYTES_PER_ARRAY is cut to a fixed seeded sample of its rows, in order,
+    the same from run to run."""
+    def f64(name, a):
+        if a.dtype.kind in "iu" and a.size and max(int(a.max()), -int(a.min())) >= 1 << 53:
+            raise RuntimeError("--dump-outputs: %s holds an integer float64 cannot carry" % name)
+        return a.astype(np.float64)
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"way_ids": f64("way_ids", res.way_ids), "hist": f64("hist", hist),
+              "speed_sum": f64("speed_sum", speed_sum)}
+    for name in ("traces", "segments", "reports"):
+        a = getattr(res, name)
+        arrays[name] = np.stack([f64("%s.%s" % (name, f), a[f]) for f in a.dtype.names if f != "pad"], axis=1)
+    for name, a in arrays.items():
+        rows = max(1, DUMP_BYTES_PER_ARRAY // (8 * (a.shape[1] if a.ndim > 1 else 1)))
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(20).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def log(rank, *a):
@@ -552,13 +600,18 @@ def main():
     import threading
     ticket = itertools.count()  # next step to run; next() is atomic under the GIL
     gate = threading.Barrier(inflight + 1)
+    last_ticket = [-1] * inflight  # per context: the last step it ran (the window's last step's results are there)
 
     def worker(i):
         gate.wait()
         if args.stagger_ms > 0:
             time.sleep(i * args.stagger_ms / 1e3)
-        while next(ticket) < args.steps:
+        while True:
+            k = next(ticket)
+            if k >= args.steps:
+                break
             step(i)
+            last_ticket[i] = k
 
     threads = [threading.Thread(target=worker, args=(i,)) for i in range(inflight)]
     for t in threads:
@@ -575,24 +628,36 @@ def main():
     elapsed = flush.close_window(t_start, hist, hist_out=hist_shard, speed_sum=speed_sum, speed_out=speed_shard,
                                  sync=lambda: torch.cuda.synchronize(dev))
 
+    if args.dump_outputs and rank == 0:
+        # what the window's last step returned: its batch's records (on the
+        # context that ran it) and the window's histogram (the reduce-scatter's
+        # shard when N > 1)
+        if args.steps < 1:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        last = engines[max(range(inflight), key=lambda i: last_ticket[i])].fetch()
+        dump_outputs(args.dump_outputs, last, (hist_shard if world > 1 else hist).cpu().numpy(),
+                     (speed_shard if world > 1 else speed_sum).cpu().numpy())
+
     # kernel spans: the same K steps again with HIP events around every launch
     # (on the launch stream); kept out of the timed region, whose throughput
     # the ~40 event records per step would perturb
-    eng.set_timing(True)
-    kern_tot = {}
-    for _ in range(args.steps):
-        step(0)
-        for k, v in eng.kernel_ms().items():
-            kern_tot[k] = kern_tot.get(k, 0.0) + v
-    torch.cuda.synchronize(dev)
-    eng.set_timing(False)
+    kern_avg = None
+    if args.full:
+        eng.set_timing(True)
+        kern_tot = {}
+        for _ in range(args.steps):
+            step(0)
+            for k, v in eng.kernel_ms().items():
+                kern_tot[k] = kern_tot.get(k, 0.0) + v
+        torch.cuda.synchronize(dev)
+        eng.set_timing(False)
+        kern_avg = {k: v / args.steps for k, v in kern_tot.items()}
     for p_ in own_streams:  # (the device leg is done with them)
         _lib.lib().otm_stream_destroy(p_)
     own_streams = []
-    kern_avg = {k: v / args.steps for k, v in kern_tot.items()}
     # the device leg's results (its last batch on eng), for the oracle check
     # below -- before the host and JSON legs run other batches on eng
-    res = eng.fetch()
+    res = None if args.no_check else eng.fetch()
     total_points = P * world * args.steps
     value = total_points / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
@@ -964,12 +1029,12 @@ def main():
     # probe's bytes where the index replaces the oracle's bounded searches
     # (transitions); the §8(d) bytes of those searches are reported beside it
     # as an equivalent-work rate, never as `frac`
-    dom_live = max(kern_avg, key=lambda k: kern_avg[k])
-    dom, dom_src = rocprof_dominant(CONFIG_ROCPROF.get(args.config), set(kern_avg))
-    if dom is None:
-        dom, dom_src = dom_live, None
     roof = None
     if sbytes is not None:
+        dom_live = max(kern_avg, key=lambda k: kern_avg[k])
+        dom, dom_src = rocprof_dominant(CONFIG_ROCPROF.get(args.config), set(kern_avg))
+        if dom is None:
+            dom, dom_src = dom_live, None
         st = KERNEL_STAGE[dom]
         sec = kern_avg[dom] * 1e-3
         own = sbytes.get(st)

@@ -5,6 +5,6 @@ set -e
 O=gpurun_out/${1:-hwqb}
 mkdir -p $O
 for q in 4 16 8; do
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-check \
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-check \
     > $O/q$q.json 2> $O/q$q.err
 done

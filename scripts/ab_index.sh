@@ -6,7 +6,7 @@ set -e
 mkdir -p gpurun_out/abi
 run() {
   name=$1; lib=$2; shift 2
-  OTM_LIB=$lib timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline --host-steps 0 --json-calls 0 "$@" \
+  OTM_LIB=$lib timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --host-steps 0 --json-calls 0 "$@" \
     > gpurun_out/abi/$name.json 2> gpurun_out/abi/$name.err
 }
 B=reporter_amd/lib/libotmatch.so

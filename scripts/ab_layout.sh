@@ -10,7 +10,7 @@ for r in $(seq 1 ${AB_ROUNDS:-2}); do
     for v in "$@"; do
       if [ "$v" = base ]; then L=reporter_amd/lib/libotmatch.so; else L=reporter_amd/lib/variants/$v/libotmatch.so; fi
       S=30; [ $c != 2 ] && S=8
-      OTM_LIB=$L timeout -k 10 300 python -u bench.py --config $c --steps $S --warmup 3 --no-cpu-baseline \
+      OTM_LIB=$L timeout -k 10 300 python -u bench.py --full --config $c --steps $S --warmup 3 --no-cpu-baseline \
         --json-calls 0 --host-steps 0 > gpurun_out/abl/$v.c$c.$r.json 2> gpurun_out/abl/$v.c$c.$r.err
     done
   done

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line (the last line of the file)."""
+"""One-screen summary of a `bench.py --full` JSON line (the last line of the file)."""
 import json
 import sys
 

@@ -18,9 +18,9 @@ done
 FAST="--no-check --no-cpu-baseline --host-steps 0 --json-calls 0 --stream-runs 0"
 for rep in 1 2; do
   for v in "$@"; do
-    OTM_LIB=$(lib $v) timeout -k 10 200 python -u bench.py $FAST --steps 200 --warmup 10 > $O/bench_c2_${v}_$rep.json 2> $O/bench_c2_${v}_$rep.err
+    OTM_LIB=$(lib $v) timeout -k 10 200 python -u bench.py --full $FAST --steps 200 --warmup 10 > $O/bench_c2_${v}_$rep.json 2> $O/bench_c2_${v}_$rep.err
   done
 done
 for v in "$@"; do
-  OTM_LIB=$(lib $v) timeout -k 10 400 python -u bench.py --config 4 --steps 10 --warmup 2 $FAST > $O/bench_c4_$v.json 2> $O/bench_c4_$v.err
+  OTM_LIB=$(lib $v) timeout -k 10 400 python -u bench.py --full --config 4 --steps 10 --warmup 2 $FAST > $O/bench_c4_$v.json 2> $O/bench_c4_$v.err
 done

@@ -12,6 +12,6 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_report.py tests/test_gpu_re
 J="--steps 5 --warmup 2 --no-cpu-baseline --no-check --host-steps 0 --json-calls 5 --single-requests 0"
 V=$R/reporter_amd/lib/variants/apool/libotmatch.so
 for i in 1 2; do
-  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py $J > $O/a_$i.json 2> $O/a_$i.err
-  OTM_JSON_PROFILE=1 OTM_LIB=$V timeout -k 10 300 python -u bench.py $J > $O/b_$i.json 2> $O/b_$i.err
+  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py --full $J > $O/a_$i.json 2> $O/a_$i.err
+  OTM_JSON_PROFILE=1 OTM_LIB=$V timeout -k 10 300 python -u bench.py --full $J > $O/b_$i.json 2> $O/b_$i.err
 done

@@ -15,4 +15,4 @@ for i in 1 2 3; do
   ARENA=1 OTM_JSON_PROFILE=1 OTM_LIB=$R/reporter_amd/lib/variants/$B/libotmatch.so timeout -k 10 120 python -u scripts/bench_async.py > $O/b_$i.json 2> $O/b_$i.err
 done
 FAST="--no-cpu-baseline --no-check --host-steps 0 --json-calls 0"
-OTM_INDEX_BUDGET_MB=60000 timeout -k 10 500 python -u bench.py --config 3 --steps 5 --warmup 2 $FAST > $O/bench_c3_budget_60000.json 2> $O/bench_c3_budget_60000.err
+OTM_INDEX_BUDGET_MB=60000 timeout -k 10 500 python -u bench.py --full --config 3 --steps 5 --warmup 2 $FAST > $O/bench_c3_budget_60000.json 2> $O/bench_c3_budget_60000.err

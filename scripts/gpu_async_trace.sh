@@ -10,5 +10,5 @@ cd $R
   --output-format csv -d $R/$O/trace -o run -- python3 $R/scripts/bench_async.py > $R/$O/trace.json 2> $R/$O/trace.err)
 FAST="--no-cpu-baseline --no-check --host-steps 0 --json-calls 0"
 for v in 6000 8000 10000 12000 16000; do
-  timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --vehicles $v $FAST > $O/vit_$v.json 2> $O/vit_$v.err
+  timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --vehicles $v $FAST > $O/vit_$v.json 2> $O/vit_$v.err
 done

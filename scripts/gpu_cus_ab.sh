@@ -11,6 +11,6 @@ V=$R/reporter_amd/lib/variants/cus/libotmatch.so
 OTM_LIB=$V timeout -k 10 400 python -u -m pytest tests/test_gpu_report.py tests/test_gpu_requests.py tests/test_gpu_group.py -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_cus.log 2>&1
 J="--no-cpu-baseline --no-check --json-calls 5 --single-requests 0"
 for i in 1 2; do
-  timeout -k 10 400 python -u bench.py $J > $O/a_$i.json 2> $O/a_$i.err
-  OTM_LIB=$V timeout -k 10 400 python -u bench.py $J > $O/b_$i.json 2> $O/b_$i.err
+  timeout -k 10 400 python -u bench.py --full $J > $O/a_$i.json 2> $O/a_$i.err
+  OTM_LIB=$V timeout -k 10 400 python -u bench.py --full $J > $O/b_$i.json 2> $O/b_$i.err
 done

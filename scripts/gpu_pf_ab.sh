@@ -11,10 +11,10 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_sc
 F="--no-cpu-baseline --no-check --host-steps 0 --json-calls 0"
 V=$R/reporter_amd/lib/variants/nopf/libotmatch.so
 for i in 1 2; do
-  timeout -k 10 300 python -u bench.py --steps 30 --warmup 5 $F > $O/a2_$i.json 2> $O/a2_$i.err
-  OTM_LIB=$V timeout -k 10 300 python -u bench.py --steps 30 --warmup 5 $F > $O/b2_$i.json 2> $O/b2_$i.err
+  timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 5 $F > $O/a2_$i.json 2> $O/a2_$i.err
+  OTM_LIB=$V timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 5 $F > $O/b2_$i.json 2> $O/b2_$i.err
 done
 for i in 1 2; do
-  timeout -k 10 400 python -u bench.py --config 4 --steps 8 --warmup 2 $F > $O/a4_$i.json 2> $O/a4_$i.err
-  OTM_LIB=$V timeout -k 10 400 python -u bench.py --config 4 --steps 8 --warmup 2 $F > $O/b4_$i.json 2> $O/b4_$i.err
+  timeout -k 10 400 python -u bench.py --full --config 4 --steps 8 --warmup 2 $F > $O/a4_$i.json 2> $O/a4_$i.err
+  OTM_LIB=$V timeout -k 10 400 python -u bench.py --full --config 4 --steps 8 --warmup 2 $F > $O/b4_$i.json 2> $O/b4_$i.err
 done

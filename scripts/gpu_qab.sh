@@ -10,6 +10,6 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_requests.py tests/test_gpu_
 bash scripts/gpu_json_kprof.sh ${1:-r05_qab}/jk
 J="--steps 5 --warmup 2 --no-cpu-baseline --no-check --json-calls 5 --single-requests 0"
 for i in 1 2; do
-  timeout -k 10 300 python -u bench.py $J > $O/a_$i.json 2> $O/a_$i.err
+  timeout -k 10 300 python -u bench.py --full $J > $O/a_$i.json 2> $O/a_$i.err
   PYTHONPATH=$R timeout -k 10 300 python -u scripts/_bench_prev.py $J > $O/b_$i.json 2> $O/b_$i.err
 done

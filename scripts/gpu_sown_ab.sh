@@ -11,6 +11,6 @@ cd $R
 J="--steps 20 --warmup 3 --no-cpu-baseline --no-check --json-calls 6 --single-requests 0"
 V=$R/reporter_amd/lib/variants/sown/libotmatch.so
 for i in 1 2; do
-  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py $J > $O/a_$i.json 2> $O/a_$i.err
-  OTM_JSON_PROFILE=1 OTM_LIB=$V timeout -k 10 300 python -u bench.py $J > $O/b_$i.json 2> $O/b_$i.err
+  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py --full $J > $O/a_$i.json 2> $O/a_$i.err
+  OTM_JSON_PROFILE=1 OTM_LIB=$V timeout -k 10 300 python -u bench.py --full $J > $O/b_$i.json 2> $O/b_$i.err
 done

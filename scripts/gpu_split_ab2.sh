@@ -11,7 +11,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_report.py -m gpu -x -v --ti
 J="--steps 5 --warmup 2 --no-cpu-baseline --no-check --host-steps 0 --json-calls 8 --async-rounds 0 --single-requests 0"
 V=$R/reporter_amd/lib/variants
 for i in 1 2; do
-  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py $J > $O/a_$i.json 2> $O/a_$i.err
-  OTM_JSON_PROFILE=1 OTM_LIB=$V/nosplit/libotmatch.so timeout -k 10 300 python -u bench.py $J > $O/b_$i.json 2> $O/b_$i.err
-  OTM_JSON_PROFILE=1 OTM_LIB=$V/s40/libotmatch.so timeout -k 10 300 python -u bench.py $J > $O/c_$i.json 2> $O/c_$i.err
+  OTM_JSON_PROFILE=1 timeout -k 10 300 python -u bench.py --full $J > $O/a_$i.json 2> $O/a_$i.err
+  OTM_JSON_PROFILE=1 OTM_LIB=$V/nosplit/libotmatch.so timeout -k 10 300 python -u bench.py --full $J > $O/b_$i.json 2> $O/b_$i.err
+  OTM_JSON_PROFILE=1 OTM_LIB=$V/s40/libotmatch.so timeout -k 10 300 python -u bench.py --full $J > $O/c_$i.json 2> $O/c_$i.err
 done

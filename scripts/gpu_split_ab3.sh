@@ -10,6 +10,6 @@ J="--steps 5 --warmup 2 --no-cpu-baseline --no-check --host-steps 0 --json-calls
 V=$R/reporter_amd/lib/variants
 for i in 1 2; do
   for v in s40 s50 s60 t50; do
-    OTM_LIB=$V/$v/libotmatch.so timeout -k 10 300 python -u bench.py $J > $O/${v}_$i.json 2> $O/${v}_$i.err
+    OTM_LIB=$V/$v/libotmatch.so timeout -k 10 300 python -u bench.py --full $J > $O/${v}_$i.json 2> $O/${v}_$i.err
   done
 done

@@ -5,7 +5,7 @@
 set -e
 R=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --traffic-json none --inflight 1"
+BENCH="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --traffic-json none --inflight 1"
 for v in "$@"; do
   if [ "$v" = base ]; then L=$R/reporter_amd/lib/libotmatch.so; else L=$R/reporter_amd/lib/variants/$v/libotmatch.so; fi
   O=$R/gpurun_out/lds/$v

@@ -9,7 +9,7 @@ for c in ${PMC_CONFIGS:-2 4}; do
   mkdir -p $O
   A="--config $c --steps 2 --warmup 1"
   (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 180 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- \
-     python3 $R/bench.py $A --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --traffic-json none --inflight 1 \
+     python3 $R/bench.py --full $A --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --traffic-json none --inflight 1 \
      > $O/kt.log 2>&1)
   PMC_BENCH_ARGS="$A" PMC_STATS_CSV=$O/kt/kt_kernel_stats.csv bash scripts/pmc.sh gpurun_out/$TAG/c$c r04_c$c
 done

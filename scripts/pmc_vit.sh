@@ -7,7 +7,7 @@ TAG=${1:-vitpmc}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --async-rounds 0 --single-requests 0 --traffic-json none --inflight 1 ${PMC_BENCH_ARGS:-}"
+BENCH="python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-check --host-steps 0 --json-calls 0 --async-rounds 0 --single-requests 0 --traffic-json none --inflight 1 ${PMC_BENCH_ARGS:-}"
 for v in ${PMC_FORMS:-64 8}; do
   export OTM_VIT_FORM=$v
   timeout -s KILL 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt$v -o kt -- $BENCH > $OUT/kt$v.log 2>&1
