@@ -38,7 +38,9 @@
 #include "orc_internal.h"
 #include "otm_oracle.h"
 
-#define MPD_F 111319.4954833f /* (float)(20037581.187 / 180), Batch.java:33 */
+/* metres per degree of rules 1 and 2: one digit off (float)(20037581.187 / 180) =
+ * 111319.8954833 of Batch.java:33, kept so that results stay what they were; the kernels use the same */
+#define MPD_F 111319.4954833f
 #define INF_F INFINITY
 
 #define TERR_NONE 0

@@ -28,7 +28,9 @@ namespace otm {
 
 namespace {
 
-#define MPD_F 111319.4954833f  // (float)(20037581.187 / 180), Batch.java:33
+// metres per degree of rules 1 and 2: one digit off (float)(20037581.187 / 180) =
+// 111319.8954833 of Batch.java:33, kept so that results stay what they were; the oracle uses the same
+#define MPD_F 111319.4954833f
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr unsigned long long LAB_NONE = ~0ull;
 constexpr int TB = 64;  // one wavefront per workgroup for the wave kernels
