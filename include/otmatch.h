@@ -385,7 +385,8 @@ int otm_index_info(const otm_engine* eng, float* rmax, int64_t* entries,
 int otm_index_levels(const otm_engine* eng, float* radii, int64_t* entries, int cap);
 
 /* The route index's device tables, full and near indexes together: hash
- * slots and their bytes (16 B a slot, the label's predecessor inside), and
+ * slots and the index's bytes (16 B a slot, the label's predecessor inside,
+ * plus each index's per-edge source records, 48 B an edge), and
  * the full index's table load in percent -- 30 when the tables fit half the
  * free HBM (53 B per entry), else 40 (40 B per entry) before the radius is
  * cut. */

@@ -2011,7 +2011,7 @@ int otm_index_tables(const otm_engine* E, int64_t* slots, int64_t* bytes, int32_
   if (!E->members.empty()) E = E->members[0];
   const int64_t n = E->index_slots + E->index_near_slots;
   if (slots) *slots = n;
-  if (bytes) *bytes = n * otm::IDX_SLOT_BYTES;
+  if (bytes) *bytes = n * otm::IDX_SLOT_BYTES + E->index_src_bytes;  // tables and per-edge source records
   if (load_pct) *load_pct = E->idx.rmax > 0.0f ? E->idx.load_pct : 0;
   return OTM_OK;
 }

@@ -427,6 +427,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->index_entries = P->index_entries;
   C->index_slots = P->index_slots;
   C->index_near_slots = P->index_near_slots;
+  C->index_src_bytes = P->index_src_bytes;
   C->index_incomplete_rows = P->index_incomplete_rows;
   C->index_build_ms = P->index_build_ms;
   C->small_points = P->small_points;
@@ -476,7 +477,7 @@ static float auto_index_radius(const otm_engine* E) {
 namespace {
 struct IndexBuilt {
   DevIndex X{};
-  int64_t entries = 0, slots = 0;
+  int64_t entries = 0, slots = 0, src_bytes = 0;
   int32_t incomplete = 0;
 };
 // One index at radius *r: count, size + scan, insert.  The tables take the
@@ -500,6 +501,8 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   HIPCHK(hipMalloc(&tmp, tmpb));
   int64_t total = 0;
   int pct = index_load_fast();
+  // the per-edge source records (kernels.h SrcRec) are part of the index: in its budget
+  const double src_bytes = (double)E->g.n_edges * sizeof(SrcRec);
   auto size_rows = [&](int load) -> int {
     launch_row_sizes(row_cnt, row_off, N, load, s);
     scan_i64(row_off, N, tmp, tmpb, s);
@@ -511,13 +514,13 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   for (int attempt = 0;; ++attempt) {
     launch_index_build(E->g, E->dp.turn_units, index_cost_bound(*r), row_cnt, nullptr, nullptr, false, s);
     if (size_rows(pct)) return OTM_EDEVICE;
-    if (pct != index_load_dense() && ((double)total + 1.0) * IDX_SLOT_BYTES > (double)budget) {
+    if (pct != index_load_dense() && ((double)total + 1.0) * IDX_SLOT_BYTES + src_bytes > (double)budget) {
       // the same rows, denser tables -- and denser from here on: a radius
       // cut below costs the online tiers far more than the denser probes
       pct = index_load_dense();
       if (size_rows(pct)) return OTM_EDEVICE;
     }
-    const double need = ((double)total + 1.0) * IDX_SLOT_BYTES;
+    const double need = ((double)total + 1.0) * IDX_SLOT_BYTES + src_bytes;
     if (need <= (double)budget) break;
     const float rr = (float)(std::floor(*r * std::sqrt((double)budget / need) * 0.9 / 50.0) * 50.0);
     if (!shrink || attempt == 4 || rr < 100.0f) {
@@ -540,6 +543,11 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   HIPCHK(hipMemsetAsync(slot, 0xFF, ((size_t)total + 1) * IDX_SLOT_BYTES, s));
   launch_index_build(E->g, E->dp.turn_units, index_cost_bound(*r), row_cnt, rows, (uint4*)slot, true, s);
   HIPCHK(hipGetLastError());
+  SrcRec* src = nullptr;
+  HIPCHK(hipMalloc(&src, ((size_t)E->g.n_edges + 1) * sizeof(SrcRec)));
+  E->graph_allocs.push_back(src);
+  launch_src_pack(E->g, rows, src, s);
+  HIPCHK(hipGetLastError());
   std::vector<int32_t> cnt((size_t)N);
   HIPCHK(hipMemcpyAsync(cnt.data(), row_cnt, (size_t)N * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -551,6 +559,8 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   out.X.rmax = *r;
   out.X.cmax = index_cost_bound(*r);
   out.X.row = rows;
+  out.X.src = src;
+  out.src_bytes = (int64_t)E->g.n_edges * (int64_t)sizeof(SrcRec);
   out.X.slot = (const uint4*)slot;
   out.X.load_pct = pct;
   return OTM_OK;
@@ -587,6 +597,7 @@ int build_index(otm_engine* E, std::string* err) {
   E->idx = full.X;
   E->index_entries = full.entries;
   E->index_slots = full.slots;
+  E->index_src_bytes = full.src_bytes;
   E->index_incomplete_rows = full.incomplete;
   // the near indexes: the same rows at smaller radii, each for the columns
   // whose bound it is the smallest to cover (its tables a fraction of the
@@ -610,6 +621,7 @@ int build_index(otm_engine* E, std::string* err) {
     if (rn > 0.0f) {
       E->index_near_level_entries[nl] = near.entries;
       E->index_near_slots += near.slots;
+      E->index_src_bytes += near.src_bytes;
       E->idxn[nl++] = near.X;
     }
   }

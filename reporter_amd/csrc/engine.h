@@ -86,6 +86,7 @@ struct otm_engine {
   int64_t index_entries = 0;
   int64_t index_slots = 0;       // hash-table slots of the full index (16 B each, the predecessor inside)
   int64_t index_near_slots = 0;  // ... of its near indexes
+  int64_t index_src_bytes = 0;   // per-edge source records (otm::SrcRec) of the full index and the near ones
   int32_t index_incomplete_rows = 0;
   float index_build_ms = 0.0f;
   otm::MatchConfig mc;

@@ -122,10 +122,36 @@ struct IdxRow {
   int32_t cnt;    // entries, -1 incomplete
   uint32_t cap;   // table slots (0 for an empty or incomplete row)
 };
+// Per-edge source record of an index (built once with it): both rows a
+// transition or route source on edge e can stand for -- row e (an edge
+// candidate) and row E + from(e) (a node candidate) -- beside the edge's from
+// node and length, so that the row descriptor's address depends on the
+// candidate record {edge, offset} alone and its load leaves with the
+// {from, length} pair's, not behind it (k_trans_sub, k_route_index).  Padded
+// to OTM_SRC_REC_BYTES, 48: the 40 B of payload in the fewest 16-B pieces.  At
+// 64 a record never straddles a 128-B line, but the records take a third more
+// lines of cache: config 4's k_trans_sub 1.340 ms at 64 against 1.328 at 48
+// (1.389 without the records; config 2 the same at both).
+#ifndef OTM_SRC_REC
+#define OTM_SRC_REC 1  // 0: the sources read DevGraph::e_fl, then DevIndex::row (A/B)
+#endif
+#ifndef OTM_SRC_REC_BYTES
+#define OTM_SRC_REC_BYTES 48
+#endif
+struct alignas(16) SrcRec {
+  IdxRow edge;     // row e
+  IdxRow node;     // row E + from(e)
+  int32_t from;    // from(e)
+  int32_t len;     // len(e), float bits
+  int32_t pad[(OTM_SRC_REC_BYTES - 40) / 4];
+};
+static_assert(sizeof(SrcRec) == OTM_SRC_REC_BYTES && (OTM_SRC_REC_BYTES == 48 || OTM_SRC_REC_BYTES == 64),
+              "source records of 48 or 64 bytes");
 struct DevIndex {
   float rmax;     // 0: no index
   uint32_t cmax;  // its cost bound, floor(rmax x 64)
   const IdxRow* row;   // [E + N]
+  const SrcRec* src;   // [E] the rows and {from, length} of each edge as a source (nullptr: no index)
   const uint4* slot;    // 16 B per slot: 53 B per entry at 30 % load, 40 B at 40 %
   int load_pct;         // the tables' load
 };
@@ -388,6 +414,8 @@ bool fold_bookkeeping();
 void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out,
                    hipStream_t s);
 void launch_row_pack(const int32_t* row_cnt, const int64_t* row_off, IdxRow* rows, int32_t n, hipStream_t s);
+// an index's per-edge source records from its packed rows and the graph's {from, length} pairs
+void launch_src_pack(const DevGraph& g, const IdxRow* rows, SrcRec* src, hipStream_t s);
 // the /report request bytes read on the GPU (requests.hip): per request r of
 // [r0, r1) of the staged blob (bytes [off[r], off[r+1])), accepted << 40 |
 // points in cnt[r] and ok[r], its points into the sparse arrays

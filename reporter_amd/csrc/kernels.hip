@@ -559,6 +559,21 @@ constexpr int CAND_LANE_CAP = OTM_CAND_LANE_CAP;
 #define OTM_CAND_WAVES 8
 #endif
 constexpr int CAND_TB = OTM_CAND_TB;
+// lane tier: where a kept entry's offset along its edge (the snap pass's
+// projection) waits for the output loop, which then loads no graph word:
+//   2  in registers, one per list slot in snap order, found through a packed
+//      8 x 3-bit permutation word that the merge's move and the sort's swaps
+//      update (no LDS, the 64-VGPR cap and 8 waves per SIMD kept)
+//   1  in a third LDS array beside sE / sQ (96 B per thread: 6 waves per SIMD;
+//      build with OTM_CAND_WAVES=6)
+//   0  nowhere: the output loop projects each chosen edge entry again (the
+//      form up to round 6: nine more loads in two round trips per candidate)
+// k_cand_lane on config 2: 197.9 us at 0, 194.1 at 2, 211.2 at 1 (222.1 with
+// OTM_SNAP_B=4, 16 B of scratch at 80 VGPRs); config 4: 1342 at 0, 1274 at 2
+// (profiles/graph_words/)
+#ifndef OTM_CAND_OFF
+#define OTM_CAND_OFF 2
+#endif
 #ifndef OTM_CAND_INFL
 #define OTM_CAND_INFL 2
 #endif
@@ -597,6 +612,12 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
   __shared__ float sQ[CAND_LANE_CAP * CAND_TB];     // best squared distance
   uint32_t* E = sE + threadIdx.x;
   float* Q = sQ + threadIdx.x;
+#if OTM_CAND_OFF == 1
+  __shared__ float sO[CAND_LANE_CAP * CAND_TB];  // offset along the edge (snap pass)
+  float* O = sO + threadIdx.x;
+#elif OTM_CAND_OFF == 2
+  static_assert(CAND_LANE_CAP <= 8 && CAND_LANE_CAP % SNAP_B == 0, "3-bit slots; whole snap steps");
+#endif
   constexpr int S = CAND_TB;
   unsigned long long c_cells = 0, c_ent = 0, c_cand = 0;
   const ItemRange R = item_range(w, b, (P.order_mask & ORDER_CAND) != 0, CAND_TB);
@@ -703,7 +724,25 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
     // loads issued together (a pure function of the entry: round 6 -- the
     // entry-by-entry walk waited on 3-4 dependent loads per entry); then the
     // merge in entry order, out of LDS.
+    // The pass also keeps each entry's offset (0 for a node candidate) for the
+    // output loop.  Its squared distance is not kept: Q already holds it.  Q
+    // of an edge entry is seg_sqdist over ent_geo of the entry in E (the scan
+    // writes the two together), ent_geo holds the very floats of s_lat /
+    // s_lon that proj_load reads (engine_init copies them), and seg_sqdist is
+    // proj_calc's sqd operation for operation (no contraction): where l2 > 0
+    // the same t, elsewhere both take t = 0.
+#if OTM_CAND_OFF == 2
+    float offr[CAND_LANE_CAP];  // by snap-pass slot; perm: list slot -> snap-pass slot
+    uint32_t perm = 076543210u;
+#pragma unroll
+    for (int m0 = 0; m0 < CAND_LANE_CAP; m0 += SNAP_B) {
+      // (unrolled so that offr is indexed by constants: registers, not scratch)
+#pragma unroll
+      for (int u = 0; u < SNAP_B; ++u) offr[m0 + u] = 0.0f;
+      if (m0 >= n) continue;
+#else
     for (int m0 = 0; m0 < n; m0 += SNAP_B) {
+#endif
       uint32_t em[SNAP_B];
       ProjIn pin[SNAP_B];
 #pragma unroll
@@ -713,13 +752,16 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
       }
       int32_t vx[SNAP_B];
       bool node0[SNAP_B], at_end[SNAP_B];
+      float offv[SNAP_B];
 #pragma unroll
       for (int u = 0; u < SNAP_B; ++u) {
         vx[u] = 0;
         node0[u] = at_end[u] = false;
+        offv[u] = 0.0f;
         if (m0 + u < n) {
           float sqd, off;
           proj_calc(pin[u], lat, lon, ls, sqd, off, at_end[u]);
+          offv[u] = off;
           node0[u] = off == 0.0f;
           const int32_t e = (int32_t)(em[u] >> 4);
           if (node0[u] || at_end[u]) vx[u] = node0[u] ? g.e_from[e] : g.e_to[e];
@@ -731,8 +773,16 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         // clamped there and it has an outgoing edge
         if (node0[u] || at_end[u]) {
           const int32_t o0 = g.out_off[vx[u]], o1 = g.out_off[vx[u] + 1];
-          if (node0[u] || o1 > o0) E[(m0 + u) * S] = NODE_ENT | ((uint32_t)o0 << 4);
+          if (node0[u] || o1 > o0) {
+            E[(m0 + u) * S] = NODE_ENT | ((uint32_t)o0 << 4);
+            offv[u] = 0.0f;
+          }
         }
+#if OTM_CAND_OFF == 1
+        if (m0 + u < n) O[(m0 + u) * S] = offv[u];
+#elif OTM_CAND_OFF == 2
+        offr[m0 + u] = offv[u];
+#endif
       }
     }
     for (int m = 0; m < n; ++m) {
@@ -747,6 +797,11 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         --n;  // drop entry m: the last entry moves here and is examined next
         E[m * S] = E[n * S];
         Q[m * S] = Q[n * S];
+#if OTM_CAND_OFF == 1
+        O[m * S] = O[n * S];
+#elif OTM_CAND_OFF == 2
+        perm = (perm & ~(7u << (3 * m))) | ((perm >> (3 * n)) & 7u) << (3 * m);
+#endif
         --m;
       }
     }
@@ -772,6 +827,14 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         E[m * S] = E[j * S];
         Q[j * S] = qm;
         E[j * S] = em;
+#if OTM_CAND_OFF == 1
+        const float om = O[m * S];
+        O[m * S] = O[j * S];
+        O[j * S] = om;
+#elif OTM_CAND_OFF == 2
+        const uint32_t x = ((perm >> (3 * m)) ^ (perm >> (3 * j))) & 7u;  // swap slots m and j
+        perm ^= x << (3 * m) | x << (3 * j);
+#endif
       }
     }
     // the K chosen, in order: the point's inline blocks whole (its 8-B
@@ -795,8 +858,18 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         if (jj < K) {
           const uint32_t en = E[jj * S];
           const int32_t e = (int32_t)((en & ~NODE_ENT) >> 4);
+#if OTM_CAND_OFF == 0
           float sqd = Q[jj * S], off = 0.0f;
           if (!(en & NODE_ENT)) project(g, e, (int32_t)(en & 15u), lat, lon, ls, sqd, off);
+#elif OTM_CAND_OFF == 1
+          const float sqd = Q[jj * S], off = O[jj * S];
+#else
+          const float sqd = Q[jj * S];
+          const uint32_t sl = (perm >> (3 * jj)) & 7u;
+          float off = offr[0];
+#pragma unroll
+          for (int t = 1; t < CAND_LANE_CAP; ++t) off = sl == (uint32_t)t ? offr[t] : off;
+#endif
           e2[u] = e;
           o2[u] = off;
           emj = sqd / ds;
@@ -1558,6 +1631,29 @@ __global__ void k_row_pack(const int32_t* row_cnt, const int64_t* row_off, IdxRo
   rows[u] = IdxRow{row_off[u], row_cnt[u], (uint32_t)cap};
 }
 
+// the per-edge source records of an index (kernels.h SrcRec), from its rows
+__global__ void k_src_pack(DevGraph g, const IdxRow* rows, SrcRec* src) {
+  const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= g.n_edges) return;
+  const int2 fl = g.e_fl[e];
+  SrcRec r{};
+  r.edge = rows[e];
+  r.node = rows[(int64_t)g.n_edges + fl.x];
+  r.from = fl.x;
+  r.len = fl.y;
+  src[e] = r;
+}
+// a source's row out of its edge's record: one 16-byte load whose address
+// comes from the candidate record alone
+__device__ __forceinline__ IdxRow src_row(const SrcRec* src, int32_t e, bool node) {
+  const uint4 v = ((const uint4*)(src + e))[node ? 1 : 0];
+  IdxRow R;
+  R.off = (int64_t)((unsigned long long)v.x | (unsigned long long)v.y << 32);
+  R.cnt = (int32_t)v.z;
+  R.cap = v.w;
+  return R;
+}
+
 // K4 index tier: S lanes per column, TB / S columns in flight per wave,
 // lanes over the column's Kq x Kp (source candidate, target candidate) pairs;
 // each pair is one probe of its source's index row (row ei, or E + from(ei)
@@ -1652,12 +1748,20 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
     const uint32_t cq = index_cost_bound(bound);
     const bool idx_ok = X.rmax > 0.0f && cq <= X.cmax;
     // the near index when it covers the bound (same answers, smaller tables)
+#if OTM_SRC_REC
+    const SrcRec* xsrc = X.src;
+#else
     const IdxRow* xrow = X.row;
+#endif
     const uint4* xslot = X.slot;
 #pragma unroll
     for (int l = NEAR_LEVELS - 1; l >= 0; --l) {
       if (w.idxn[l].rmax > 0.0f && cq <= w.idxn[l].cmax) {
+#if OTM_SRC_REC
+        xsrc = w.idxn[l].src;
+#else
         xrow = w.idxn[l].row;
+#endif
         xslot = w.idxn[l].slot;
       }
     }
@@ -1680,6 +1784,25 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
         const float o = __int_as_float(c.y);
         // src_start and src_row from the edge's {from, length} pair (one
         // load); the heading only for the work counters (no load otherwise)
+#if OTM_SRC_REC
+        // with an index, both out of the edge's source record: the row that
+        // cand_node(o) selects and the length, addressed by the candidate
+        // record alone, leave together (the row's number needed from(e) first)
+        IdxRow R{};
+        int32_t lenb;
+        if (idx_ok) {
+          R = src_row(xsrc, e, cand_node(o));
+          lenb = xsrc[e].len;
+        } else {
+          lenb = g.e_fl[e].y;
+        }
+        const float start = cand_node(o) ? 0.0f : __int_as_float(lenb) - o;
+        sr[sg][k ^ swz] = make_int4(e, __float_as_int(o), __float_as_int(start), w.ctr ? (int)src_head(g, e, o) : 0);
+        if (idx_ok) {
+          rq[sg][k ^ swz] = R;
+          bad = bad || R.cnt < 0;
+        }
+#else
         const int2 fl = g.e_fl[e];
         const float start = cand_node(o) ? 0.0f : __int_as_float(fl.y) - o;
         sr[sg][k ^ swz] = make_int4(e, __float_as_int(o), __float_as_int(start), w.ctr ? (int)src_head(g, e, o) : 0);
@@ -1688,6 +1811,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
           rq[sg][k ^ swz] = R;
           bad = bad || R.cnt < 0;
         }
+#endif
       }
     }
     const bool spill = (__ballot(bad) & smask) != 0ull;
@@ -1872,12 +1996,24 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
     for (int l = NEAR_LEVELS - 1; l >= 0; --l)
       if (w.idxn[l].rmax > 0.0f && cq <= w.idxn[l].cmax) lvl = l;
     const DevIndex& Xc = lvl >= 0 ? w.idxn[lvl] : X;
+#if OTM_SRC_REC
+    // the source's row and length out of its edge's source record: the row's
+    // address from the chosen candidate alone, the length beside it
+    int32_t leni = 0;
+    if (X.rmax > 0.0f && cq <= X.cmax) {
+      Rw = src_row(Xc.src, ei, cand_node(oi));
+      leni = Xc.src[ei].len;
+      sv = idx_find(Xc.slot, Rw, dst_key(g, ej, oj), lab);
+    }
+#else
     // the source's row and start from its edge's {from, length} pair (one load)
     const int2 fli = g.e_fl[ei];
+    const int32_t leni = fli.y;
     if (X.rmax > 0.0f && cq <= X.cmax) {
       Rw = Xc.row[cand_node(oi) ? (int64_t)g.n_edges + fli.x : (int64_t)ei];
       sv = idx_find(Xc.slot, Rw, dst_key(g, ej, oj), lab);
     }
+#endif
     if (sv < 0 || idx_slot_cost(lab) > cq) {
       const int slot = atomicAdd(&w.counters_i32[4], 1);
       w.overflow_list0[slot] = (int32_t)p;
@@ -1902,7 +2038,7 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
       w.path_off[p] = off;
       w.path_len[p] = len;
     }
-    const float start = cand_node(oi) ? 0.0f : __int_as_float(fli.y) - oi;  // src_start
+    const float start = cand_node(oi) ? 0.0f : __int_as_float(leni) - oi;  // src_start
     const float sd = start + bitsf(lab.z);
     w.route_dist[p] = sd + oj;
     if (w.ctr) {
@@ -4229,6 +4365,11 @@ void launch_candidates(const DevGraph& g, const DevBatch& b, const DevParams& p,
                                              dim3(CAND_TB), 0, s, g, b, p, w));
   }
   mk.begin(KN_CAND_WAVE, s);
+  // (a fixed 4096 waves, each walking two or three of config 2's ~10k spilled
+  // probes in a row.  Not kept: the grid sized from the batch, a wave per
+  // expected spilled probe (n_points / 64 between 256 and 16384: 15,625 waves
+  // at 1M points) -- 37.7 against 36.0 us on config 2, 8.5 against 7.8 on
+  // config 4, profiles/graph_words/kernels.json build "c")
   if (from < RESUME_CAND_BIG) hipLaunchKernelGGL(k_candidates<false>, dim3(4096), dim3(TB), 0, s, g, b, p, w);
   hipLaunchKernelGGL(k_candidates<true>, dim3(CAND_BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
   mk.end(KN_CAND_WAVE, s);
@@ -4419,6 +4560,10 @@ void launch_row_sizes(const int32_t* row_cnt, int64_t* row_sizes, int32_t n, int
 }
 void launch_row_pack(const int32_t* row_cnt, const int64_t* row_off, IdxRow* rows, int32_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_row_pack, dim3(grid_for((int64_t)n, 256, 1 << 30)), dim3(256), 0, s, row_cnt, row_off, rows, n);
+}
+void launch_src_pack(const DevGraph& g, const IdxRow* rows, SrcRec* src, hipStream_t s) {
+  if (g.n_edges <= 0) return;
+  hipLaunchKernelGGL(k_src_pack, dim3(grid_for((int64_t)g.n_edges, 256, 1 << 30)), dim3(256), 0, s, g, rows, src);
 }
 
 size_t scan_tmp_bytes(int64_t n) {
