@@ -361,6 +361,84 @@ int otm_hist_bind(otm_engine* eng, void* dev_counts, int nbins, float bin_kph);
  * engine's clones at their next batch. */
 int otm_hist_bind_ex(otm_engine* eng, void* dev_counts, int nbins, float bin_kph,
                      void* dev_speed_sum);
+
+/* ------------------------------------------------------ the datastore flush
+ * What becomes of the histogram: the body a reporter POSTs to DATASTORE_URL
+ * (a TODO in the reference, docker-compose.yml:17; here the format of
+ * reporter_amd/datastore.py, serialize(flush_records(...)), which these calls
+ * replace for a host without Python).  Compact JSON, rows ascending, only rows
+ * whose bins sum to more than 0, never a row at or past n_segments (padding
+ * rows carry no id):
+ *   {"mode":"auto","bin_kph":<repr>,"rank":R,"world":W,"segments":[
+ *    {"id":<u64>,"count":<sum of bins>,"speed_sum_kph":<repr(sum/1000.0)>,
+ *     "bins":[b0,...,b(nbins-1)]},...]}
+ * bin_kph is the float widened to double and written as Python's repr, as is
+ * (double)sum / 1000.0 (bit-identical to Python's int / float for every u64).
+ * The slice is rank `rank` of `world`: `rows` = S_pad / world rows, slice row k
+ * being global row rank * rows + k.  Preconditions: bins are read as u32; the
+ * Python definition is stated for bins below 2^31 (it goes through int32
+ * tensors).  *body is NUL-terminated (the NUL not counted in *body_len) and
+ * released with otm_free; n_records may be NULL.  Errors: OTM_EINVAL with a
+ * message in otm_last_error (NULL pointers, nbins < 1, bin_kph <= 0,
+ * world < 1, rank outside [0, world)). */
+
+/* The body written on the host: no GPU, no engine (a host that reduced its
+ * histograms on the CPU; also what the device writer falls back to).  Total:
+ * every double a u64 / 1000.0 can give is written as repr writes it, the
+ * exponent form from 1e16 up included.  counts u32[rows * nbins], speed_sum
+ * u64[rows], segment_ids u64[n_segments] in host memory. */
+int otm_flush_body_host(const uint32_t* counts, const uint64_t* speed_sum,
+                        const uint64_t* segment_ids, int64_t n_segments,
+                        int64_t rows, int nbins, float bin_kph, int rank, int world,
+                        char** body, size_t* body_len, int64_t* n_records);
+/* The same bytes from a slice in device memory (what flush.reduce_histograms
+ * returns, or a whole window with world 1), written on the GPU: one read of
+ * the slice, the records formatted and packed there, and only the body's bytes
+ * copied to the host; one host sync.  The ids are the engine's own HBM copy of
+ * the graph's; a multi-device engine answers with member 0's graph, or with
+ * the member on whose device the buffers lie.  `stream` is a hipStream_t the
+ * buffers are ready on (NULL: the engine's own).  nbins at most 64 on this
+ * path (OTM_EINVAL past it; otm_flush_body_host has no limit).  A speed sum of
+ * 2^52 x 1000 or more is outside the GPU float writer's range: the slice is
+ * then copied to the host and written there -- the same bytes, slower.  The
+ * call serialises with the engine's batches; its scratch stays with the engine
+ * at the size it grew to.  Sizing HBM: that scratch is one record slot per row
+ * of the slice whatever the window's density -- rows x (108 + 11 x nbins)
+ * bytes, rounded up to 8 per slot (288 B a row at 16 bins: 279 MB for 968k
+ * rows; 816 B a row at 64 bins) -- plus 8 bytes a row of lengths and a blob
+ * of the largest body seen. */
+int otm_flush_body_device(otm_engine* eng, const void* dev_counts,
+                          const void* dev_speed_sum, int64_t rows, int nbins,
+                          float bin_kph, int rank, int world, void* stream,
+                          char** body, size_t* body_len, int64_t* n_records);
+
+/* Engine-owned windows: the histogram in library-owned device memory, for a
+ * host that cannot allocate any (a JVM).  otm_window_begin allocates zeroed
+ * counts and speed sums for the engine's segments and binds them exactly as
+ * otm_hist_bind_ex would (clones pick the binding up at their next batch); on
+ * a multi-device engine one pair per member, on that member's device (the
+ * public otm_hist_bind* keep refusing a multi-device engine).
+ * otm_window_flush closes the window: it waits for the work of the engine's
+ * devices, adds the members' pairs into member 0's on the GPU (a member on
+ * another device arrives by a peer copy), writes the body of the whole window
+ * (rank 0, world 1) as otm_flush_body_device does, zeroes every buffer, and
+ * the window goes on.  CONTRACT: no match call may be in progress on the
+ * engine, its clones or its members during otm_window_flush -- close a window
+ * between batches.  otm_window_end unbinds and frees; otm_engine_destroy ends
+ * an open window.  OTM_EINVAL (message in otm_last_error): begin on a clone,
+ * begin while a window is open or while a caller's otm_hist_bind binding is in
+ * place, otm_hist_bind* of a buffer while a window is open, flush or end
+ * without a window, nbins < 1, bin_kph <= 0, nbins past the device writer's
+ * limit (64), and any of the three calls on a member handle of a multi-device
+ * engine (otm_engine_member): a member's window belongs to the group's handle.
+ * otm_hist_bind* with a NULL buffer stays allowed while a window is open, on
+ * the engine or on a member: it unbinds the window's buffers, so counting
+ * stops silently until the window is ended and begun again; the buffers stay
+ * allocated and otm_window_flush keeps answering from them. */
+int otm_window_begin(otm_engine* eng, int nbins, float bin_kph);
+int otm_window_flush(otm_engine* eng, char** body, size_t* body_len, int64_t* n_records);
+int otm_window_end(otm_engine* eng);
+
 int otm_graph_info(const otm_engine* eng, int64_t* n_nodes, int64_t* n_edges,
                    int64_t* n_segments);
 

@@ -28,6 +28,17 @@ public final class OtmJni {
   /** The /report call on request bytes: the response bytes, or null when the call fails. */
   private static native byte[] report(byte[] body);
 
+  /**
+   * The datastore flush: an engine-owned histogram window (otm_window_begin / _flush / _end).  windowFlush,
+   * called between batches, returns the window's body -- the bytes to POST to DATASTORE_URL as configured --
+   * and the window goes on from zero.  A failure throws IllegalStateException.
+   */
+  public static native void windowBegin(int nbins, float binKph);
+
+  public static native byte[] windowFlush();
+
+  public static native void windowEnd();
+
   /** A page-locked request arena of the library (otm_request_arena_alloc) as a direct buffer. */
   private static native ByteBuffer arenaAlloc(long bytes);
 

@@ -78,6 +78,17 @@ public final class OtmMatcher {
   private static final MethodHandle LAST_ERROR = fn("otm_last_error",
       FunctionDescriptor.of(ValueLayout.ADDRESS, ValueLayout.ADDRESS));
 
+  // int otm_window_begin(otm_engine*, int nbins, float bin_kph)
+  private static final MethodHandle WINDOW_BEGIN = fn("otm_window_begin",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.JAVA_INT, ValueLayout.JAVA_FLOAT));
+  // int otm_window_flush(otm_engine*, char** body, size_t* body_len, int64_t* n_records)
+  private static final MethodHandle WINDOW_FLUSH = fn("otm_window_flush",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS, ValueLayout.ADDRESS,
+                            ValueLayout.ADDRESS));
+  // int otm_window_end(otm_engine*)
+  private static final MethodHandle WINDOW_END = fn("otm_window_end",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS));
+
   // otm_result: {uint64_t tag; int code; (4 bytes padding) char* body; size_t body_len} = 32 bytes
   private static final MemoryLayout RESULT = MemoryLayout.structLayout(ValueLayout.JAVA_LONG.withName("tag"),
       ValueLayout.JAVA_INT.withName("code"), MemoryLayout.paddingLayout(4), ValueLayout.ADDRESS.withName("body"),
@@ -162,6 +173,52 @@ public final class OtmMatcher {
     String v = new String(p.reinterpret(n).toArray(ValueLayout.JAVA_BYTE), StandardCharsets.UTF_8);
     FREE.invokeExact(p);
     return v;
+  }
+
+  private static void check(int rc, String what) throws Throwable {
+    if (rc != 0) {
+      MemorySegment msg = (MemorySegment) LAST_ERROR.invokeExact(MemorySegment.NULL);
+      throw new IllegalStateException(what + ": " + msg.reinterpret(4096).getString(0));
+    }
+  }
+
+  /**
+   * The datastore flush (include/otmatch.h, "the datastore flush"): the per-segment speed histogram of a
+   * window, kept by the library in device memory it owns.  windowBegin once; windowFlush between batches
+   * (no match call in progress on the engine) returns the window's body -- the bytes to POST to
+   * DATASTORE_URL as configured (docker-compose.yml:17; its secret_key is already in the URL) -- and the
+   * window goes on from zero; windowEnd frees it.
+   */
+  public static void windowBegin(int nbins, float binKph) {
+    try {
+      check((int) WINDOW_BEGIN.invokeExact(ENGINE, nbins, binKph), "otm_window_begin");
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /** The window's flush body (compact JSON, UTF-8); "segments":[] when nothing was reported. */
+  public static byte[] windowFlush() {
+    try (Arena a = Arena.ofConfined()) {
+      MemorySegment body = a.allocate(ValueLayout.ADDRESS);
+      MemorySegment len = a.allocate(ValueLayout.JAVA_LONG);
+      MemorySegment nrec = a.allocate(ValueLayout.JAVA_LONG);
+      check((int) WINDOW_FLUSH.invokeExact(ENGINE, body, len, nrec), "otm_window_flush");
+      MemorySegment p = body.get(ValueLayout.ADDRESS, 0);
+      byte[] v = p.reinterpret(len.get(ValueLayout.JAVA_LONG, 0)).toArray(ValueLayout.JAVA_BYTE);
+      FREE.invokeExact(p);
+      return v;
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  public static void windowEnd() {
+    try {
+      check((int) WINDOW_END.invokeExact(ENGINE), "otm_window_end");
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
   }
 
   /** Same contract as HttpClient.POST: the response body, or null on a failure of the call. */

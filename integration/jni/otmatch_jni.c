@@ -48,6 +48,39 @@ JNIEXPORT jbyteArray JNICALL Java_org_opentraffic_reporter_OtmJni_report(JNIEnv*
   return out;
 }
 
+/* OtmJni.windowBegin / windowFlush / windowEnd: the engine-owned histogram window (include/otmatch.h, "the
+ * datastore flush").  windowFlush returns the body to POST to DATASTORE_URL; a failure throws
+ * IllegalStateException with the library's message. */
+static void throw_last(JNIEnv* env) {
+  (*env)->ThrowNew(env, (*env)->FindClass(env, "java/lang/IllegalStateException"), otm_last_error(NULL));
+}
+
+JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_windowBegin(JNIEnv* env, jclass c, jint nbins,
+                                                                        jfloat bin_kph) {
+  (void)c;
+  if (otm_window_begin(g_eng, (int)nbins, (float)bin_kph) != OTM_OK) throw_last(env);
+}
+
+JNIEXPORT jbyteArray JNICALL Java_org_opentraffic_reporter_OtmJni_windowFlush(JNIEnv* env, jclass c) {
+  (void)c;
+  char* body = NULL;
+  size_t n = 0;
+  int64_t nrec = 0;
+  if (otm_window_flush(g_eng, &body, &n, &nrec) != OTM_OK) {
+    throw_last(env);
+    return NULL;
+  }
+  jbyteArray out = (*env)->NewByteArray(env, (jsize)n);
+  if (out) (*env)->SetByteArrayRegion(env, out, 0, (jsize)n, (const jbyte*)body);
+  otm_free(body);
+  return out;
+}
+
+JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_windowEnd(JNIEnv* env, jclass c) {
+  (void)c;
+  if (otm_window_end(g_eng) != OTM_OK) throw_last(env);
+}
+
 /* OtmJni.arenaAlloc(long): a library-owned page-locked request arena (otm_request_arena_alloc) as a
  * direct ByteBuffer the Java side writes its request bytes into. */
 JNIEXPORT jobject JNICALL Java_org_opentraffic_reporter_OtmJni_arenaAlloc(JNIEnv* env, jclass c, jlong bytes) {

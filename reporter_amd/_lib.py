@@ -157,6 +157,13 @@ def _declare(L):
         "otm_fetch_results": (C.c_int, [vp, C.POINTER(Results)]),
         "otm_hist_bind": (C.c_int, [vp, vp, C.c_int, C.c_float]),
         "otm_hist_bind_ex": (C.c_int, [vp, vp, C.c_int, C.c_float, vp]),
+        "otm_flush_body_host": (C.c_int, [vp, vp, vp, i64, i64, C.c_int, C.c_float, C.c_int, C.c_int, pp, psz,
+                                          C.POINTER(i64)]),
+        "otm_flush_body_device": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_float, C.c_int, C.c_int, vp, pp, psz,
+                                            C.POINTER(i64)]),
+        "otm_window_begin": (C.c_int, [vp, C.c_int, C.c_float]),
+        "otm_window_flush": (C.c_int, [vp, pp, psz, C.POINTER(i64)]),
+        "otm_window_end": (C.c_int, [vp]),
         "otm_report_segments_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), psz, C.POINTER(C.c_char_p), psz,
                                                  pp, psz, C.POINTER(C.c_int)]),
         "otm_graph_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),

@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "flush.h"
 #include "javastr.h"
 #include "json.h"
 #include "pyrepr.h"
@@ -1445,6 +1446,7 @@ static int otm_engine_create_impl(const char* cfg_path, const int* devices, int 
         delete G;
         return fail(rc, msg);
       }
+      M->group = G;
       G->members.push_back(M);
     }
     const otm_engine* L = G->members[0];
@@ -1976,6 +1978,8 @@ int otm_hist_bind_ex(otm_engine* E, void* dev_counts, int nbins, float bin_kph, 
   if (dev_speed_sum && !dev_counts) return fail(OTM_EINVAL, "a speed-sum channel needs the counts");
   // a batch in flight on this engine or a clone keeps the binding it started with
   std::lock_guard<std::mutex> lk(E->hist_mu);
+  if (dev_counts && E->win_open)
+    return fail(OTM_EINVAL, "an engine-owned window is open (otm_window_end it before binding a buffer)");
   E->hist = (uint32_t*)dev_counts;
   E->speed_sum = dev_counts ? (unsigned long long*)dev_speed_sum : nullptr;
   E->nbins = dev_counts ? nbins : 0;
@@ -1985,6 +1989,89 @@ int otm_hist_bind_ex(otm_engine* E, void* dev_counts, int nbins, float bin_kph, 
 
 int otm_hist_bind(otm_engine* E, void* dev_counts, int nbins, float bin_kph) {
   return otm_hist_bind_ex(E, dev_counts, nbins, bin_kph, nullptr);
+}
+
+// flush_host.cpp reports its argument errors through this (it links without
+// abi.cpp too); hidden: not part of the library's surface
+__attribute__((visibility("hidden"))) void otm_set_last_error(const char* msg) { fail(OTM_EINVAL, msg ? msg : ""); }
+
+int otm_flush_body_device(otm_engine* E, const void* dev_counts, const void* dev_speed_sum, int64_t rows, int nbins,
+                          float bin_kph, int rank, int world, void* stream, char** body, size_t* body_len,
+                          int64_t* n_records) {
+  if (!E || !body || !body_len) return fail(OTM_EINVAL, "engine, body and body_len must not be NULL");
+  otm_engine* M = E;
+  if (!E->members.empty()) {
+    // member 0's graph, unless the slice lies on another member's device
+    M = E->members[0];
+    hipPointerAttribute_t at{};
+    if (dev_counts && hipPointerGetAttributes(&at, dev_counts) == hipSuccess) {
+      for (otm_engine* m : E->members)
+        if (m->device == at.device && M->device != at.device) M = m;
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  std::string err;
+  int rc;
+  try {
+    std::lock_guard<std::mutex> lk(M->mu);
+    rc = otm::engine_flush_body(M, dev_counts, dev_speed_sum, rows, nbins, bin_kph, rank, world, (hipStream_t)stream,
+                                body, body_len, n_records, &err);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_window_begin(otm_engine* E, int nbins, float bin_kph) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (E->parent) return fail(OTM_EINVAL, "open the window on the parent engine (clones share it)");
+  if (E->group) return fail(OTM_EINVAL, "a member's window belongs to its multi-device engine: call it on that handle");
+  if (nbins < 1 || !(bin_kph > 0.0f)) return fail(OTM_EINVAL, "nbins >= 1 and bin_kph > 0");
+  if (nbins > otm::FLUSH_MAX_NBINS)
+    return fail(OTM_EINVAL, "nbins past the device writer's limit (" + std::to_string(otm::FLUSH_MAX_NBINS) + ")");
+  std::string err;
+  int rc;
+  try {
+    std::lock_guard<std::mutex> lk(E->win_mu);
+    rc = otm::engine_window_begin(E, nbins, bin_kph, &err);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_window_flush(otm_engine* E, char** body, size_t* body_len, int64_t* n_records) {
+  if (!E || !body || !body_len) return fail(OTM_EINVAL, "engine, body and body_len must not be NULL");
+  *body = nullptr;
+  *body_len = 0;
+  if (n_records) *n_records = 0;
+  if (E->parent) return fail(OTM_EINVAL, "no window is open on a clone (flush its parent's)");
+  if (E->group) return fail(OTM_EINVAL, "a member's window belongs to its multi-device engine: call it on that handle");
+  std::string err;
+  int rc;
+  try {
+    std::lock_guard<std::mutex> lk(E->win_mu);
+    rc = otm::engine_window_flush(E, body, body_len, n_records, &err);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_window_end(otm_engine* E) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (E->parent) return fail(OTM_EINVAL, "no window is open on a clone (end its parent's)");
+  if (E->group) return fail(OTM_EINVAL, "a member's window belongs to its multi-device engine: call it on that handle");
+  std::string err;
+  int rc;
+  try {
+    std::lock_guard<std::mutex> lk(E->win_mu);
+    rc = otm::engine_window_end(E, &err);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+  return rc ? fail(rc, err) : OTM_OK;
 }
 
 int otm_graph_info(const otm_engine* E, int64_t* n_nodes, int64_t* n_edges, int64_t* n_segments) {

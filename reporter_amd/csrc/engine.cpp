@@ -5,6 +5,8 @@
 // holds the flattened graph in HBM and matches whole batches of traces.
 #include "engine.h"
 
+#include "flush.h"
+
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -655,14 +657,20 @@ void engine_free(otm_engine* E) {
       &E->abort_flag,    &E->rs_blob,      &E->ord_tile,      &E->ord_cnt,      &E->ord_cursor,     &E->ord_grp,    &E->ord_item,
       &E->d_req,         &E->req_cnt,      &E->req_ok,     &E->req_lat,    &E->req_lon,    &E->req_time,   &E->req_acc,
       &E->resp_hdr,      &E->resp_seg,     &E->resp_rep,       &E->resp_hlen,      &E->resp_slen,  &E->resp_rlen,
-      &E->resp_blen,     &E->resp_host,    &E->resp_blob};
+      &E->resp_blen,     &E->resp_host,    &E->resp_blob,
+      &E->flush_slots,   &E->flush_len,    &E->flush_blob,     &E->flush_meta,     &E->win_peer_counts,
+      &E->win_peer_sums};
+  if (E->win_counts) (void)hipFree(E->win_counts);
+  if (E->win_sums) (void)hipFree(E->win_sums);
+  E->win_counts = E->win_sums = nullptr;
+  E->win_open = false;
   for (auto* b : bufs) {
     if (b->p) (void)hipFree(b->p);
     b->p = nullptr;
     b->cap = 0;
   }
   for (auto* b : {&E->h_traces, &E->h_segs, &E->h_reps_dense, &E->h_ways, &E->h_tot, &E->h_in, &E->h_status,
-                  &E->h_req, &E->h_req_ok, &E->h_resp, &E->h_resp_meta}) {
+                  &E->h_req, &E->h_req_ok, &E->h_resp, &E->h_resp_meta, &E->h_flush, &E->h_flush_meta}) {
     if (b->p) (void)hipHostFree(b->p);
     b->p = nullptr;
     b->cap = 0;
@@ -1752,6 +1760,270 @@ int engine_counters(otm_engine* E, otm_work_counters* out) {
   if (hipMemcpy(&c, E->ctr, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return OTM_EDEVICE;
   static_assert(sizeof(DevCounters) == sizeof(otm_work_counters), "counter layout");
   std::memcpy(out, &c, sizeof c);
+  return OTM_OK;
+}
+
+// ------------------------------------------------------------ datastore flush
+// The flush body of a histogram slice in E's HBM, written on the GPU
+// (flush.hip): one read of the slice, the records' bytes into page-locked host
+// memory, one host sync.  The blob and its host copy start small and grow to
+// the largest body seen (a body that outgrows them is copied a second time,
+// once); nothing is allocated per call after that.
+int engine_flush_body(otm_engine* E, const void* dev_counts, const void* dev_speed_sum, int64_t rows, int nbins,
+                      float bin_kph, int rank, int world, hipStream_t stream, char** body, size_t* body_len,
+                      int64_t* n_records, std::string* err) {
+  *body = nullptr;
+  *body_len = 0;
+  if (n_records) *n_records = 0;
+  if (nbins < 1 || nbins > FLUSH_MAX_NBINS || !(bin_kph > 0.0f)) {
+    *err = "nbins in [1, " + std::to_string(FLUSH_MAX_NBINS) + "] on the device writer, and bin_kph > 0";
+    return OTM_EINVAL;
+  }
+  if (world < 1 || rank < 0 || rank >= world) {
+    *err = "world >= 1 and 0 <= rank < world";
+    return OTM_EINVAL;
+  }
+  if (rows < 0 || rows > 0x7ffffff0ll || (rows > 0 && (!dev_counts || !dev_speed_sum))) {
+    *err = "rows in [0, 2^31) and device buffers for them";
+    return OTM_EINVAL;
+  }
+  const otm_engine* G = E->parent ? E->parent : E;  // (a clone holds the graph header alone)
+  const int64_t nseg = (int64_t)G->host.h.n_segments;
+  HIPCHK(hipSetDevice(E->device));
+  hipStream_t s = stream ? stream : E->stream;
+  const int slot = flush_slot_bytes(nbins);
+  int rc;
+  ENS_F(flush_slots, (size_t)rows * (size_t)slot + 64);
+  ENS_F(flush_len, ((size_t)rows + 1) * 8);
+  ENS_F(flush_meta, sizeof(FlushMeta));
+  ENS_F(scan_tmp, scan_tmp_bytes(rows) + 256);
+  if (!E->flush_blob.p) ENS_F(flush_blob, (size_t)1 << 20);
+  if (!E->h_flush.p && (rc = ensure_pinned(E->h_flush, (size_t)1 << 20, err))) return rc;
+  if ((rc = ensure_pinned(E->h_flush_meta, 64, err))) return rc;
+  FlushIn in{(const uint32_t*)dev_counts, (const unsigned long long*)dev_speed_sum, E->g.g_id, rows,
+             (int64_t)rank * rows, nseg, nbins};
+  int64_t* len = P<int64_t>(E->flush_len);
+  FlushMeta* meta = (FlushMeta*)E->flush_meta.p;
+  char* hm = (char*)E->h_flush_meta.p;
+  HIPCHK(hipMemsetAsync(meta, 0, sizeof(FlushMeta), s));
+  launch_flush_rows(in, P<char>(E->flush_slots), len, meta, s);
+  scan_i64(len, rows, E->scan_tmp.p, E->scan_tmp.cap, s);
+  FlushMeta m{};
+  int64_t total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const int64_t cap = (int64_t)std::min(E->flush_blob.cap, E->h_flush.cap) - 16;
+    launch_flush_copy(rows, slot, P<char>(E->flush_slots), len, P<char>(E->flush_blob), cap, s);
+    launch_flush_out(P<char>(E->flush_blob), len + rows, (char*)E->h_flush.p, cap, s);
+    if (attempt == 0) {
+      HIPCHK(hipMemcpyAsync(hm, meta, sizeof(FlushMeta), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hm + 16, len + rows, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    std::memcpy(&m, hm, sizeof m);
+    std::memcpy(&total, hm + 16, 8);
+    if (m.declined || total <= cap) break;
+    // the body outgrew the blob: grow both and copy again (the slots stand)
+    ENS_F(flush_blob, (size_t)total + 16);
+    if ((rc = ensure_pinned(E->h_flush, (size_t)total + 16, err))) return rc;
+  }
+  if (m.declined) {
+    // a speed sum past pyrepr.h's range (2^52 x 1000): the host writes the slice
+    try {
+      std::vector<uint32_t> hc((size_t)rows * (size_t)nbins);
+      std::vector<uint64_t> hs((size_t)rows);
+      HIPCHK(hipMemcpyAsync(hc.data(), dev_counts, hc.size() * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hs.data(), dev_speed_sum, hs.size() * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      return flush_body_host(hc.data(), hs.data(), G->host.g_id, nseg, rows, nbins, bin_kph, rank, world, body,
+                             body_len, n_records, err);
+    } catch (const std::bad_alloc&) {
+      *err = "out of host memory";
+      return OTM_ENOMEM;
+    }
+  }
+  // the head and tail around the records (each came with a leading comma)
+  const std::string head = flush_head(bin_kph, rank, world);
+  const size_t recs = total > 0 ? (size_t)total - 1 : 0;
+  const size_t n = head.size() + recs + 2;
+  char* p = (char*)std::malloc(n + 1);
+  if (!p) {
+    *err = "out of host memory";
+    return OTM_ENOMEM;
+  }
+  std::memcpy(p, head.data(), head.size());
+  if (recs) std::memcpy(p + head.size(), (const char*)E->h_flush.p + 1, recs);
+  std::memcpy(p + head.size() + recs, "]}", 3);
+  *body = p;
+  *body_len = n;
+  if (n_records) *n_records = (int64_t)m.n_records;
+  return OTM_OK;
+}
+
+// ------------------------------------------------------------ engine-owned windows
+static std::vector<otm_engine*> window_members(otm_engine* E) {
+  return E->members.empty() ? std::vector<otm_engine*>{E} : E->members;
+}
+
+static void window_drop(otm_engine* M) {
+  {
+    std::lock_guard<std::mutex> lk(M->hist_mu);
+    if (M->win_open) {
+      M->hist = nullptr;
+      M->speed_sum = nullptr;
+      M->nbins = 0;
+    }
+    M->win_open = false;
+  }
+  (void)hipSetDevice(M->device);
+  if (M->win_counts) (void)hipFree(M->win_counts);  // (hipFree waits for the device's work)
+  if (M->win_sums) (void)hipFree(M->win_sums);
+  M->win_counts = M->win_sums = nullptr;
+}
+
+static int window_begin_one(otm_engine* M, int nbins, float bin_kph, std::string* err) {
+  const size_t S = (size_t)M->host.h.n_segments;
+  const size_t cb = std::max<size_t>(16, S * (size_t)nbins * 4), sb = std::max<size_t>(16, S * 8);
+  void *wc = nullptr, *ws = nullptr;
+  auto drop = [&] {
+    if (wc) (void)hipFree(wc);
+    if (ws) (void)hipFree(ws);
+  };
+  hipError_t e = hipSetDevice(M->device);
+  if (e == hipSuccess) e = hipMalloc(&wc, cb);
+  if (e == hipSuccess) e = hipMalloc(&ws, sb);
+  if (e == hipSuccess) e = hipMemsetAsync(wc, 0, cb, M->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ws, 0, sb, M->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(M->stream);
+  if (e != hipSuccess) {
+    drop();
+    *err = std::string("window buffers: ") + hipGetErrorString(e);
+    return OTM_EDEVICE;
+  }
+  // bound as otm_hist_bind_ex binds (clones read it at their next batch); the
+  // check and the bind under one hold of hist_mu, so a caller's bind that
+  // raced the window's begin is refused here, not overwritten
+  std::lock_guard<std::mutex> lk(M->hist_mu);
+  if (M->win_open || M->hist) {
+    drop();
+    *err = M->win_open ? "a window is already open on this engine"
+                       : "a caller's otm_hist_bind binding is in place: unbind it before a window";
+    return OTM_EINVAL;
+  }
+  M->win_counts = wc;
+  M->win_sums = ws;
+  M->hist = (uint32_t*)wc;
+  M->speed_sum = (unsigned long long*)ws;
+  M->nbins = nbins;
+  M->bin_kph = bin_kph;
+  M->win_open = true;
+  M->win_nbins = nbins;
+  M->win_bin_kph = bin_kph;
+  return OTM_OK;
+}
+
+int engine_window_begin(otm_engine* E, int nbins, float bin_kph, std::string* err) {
+  if (E->win_open) {
+    *err = "a window is already open on this engine";
+    return OTM_EINVAL;
+  }
+  const std::vector<otm_engine*> ms = window_members(E);
+  for (otm_engine* M : ms) {
+    std::lock_guard<std::mutex> lk(M->hist_mu);
+    if (M->win_open) {
+      *err = "a window is already open on this engine";
+      return OTM_EINVAL;
+    }
+    if (M->hist) {
+      *err = "a caller's otm_hist_bind binding is in place: unbind it before a window";
+      return OTM_EINVAL;
+    }
+  }
+  for (size_t i = 0; i < ms.size(); ++i) {
+    const int rc = window_begin_one(ms[i], nbins, bin_kph, err);
+    if (rc) {
+      (void)hipGetLastError();
+      for (size_t k = 0; k < i; ++k) window_drop(ms[k]);  // (the members this call opened)
+      return rc;
+    }
+  }
+  E->win_open = true;
+  E->win_nbins = nbins;
+  E->win_bin_kph = bin_kph;
+  return OTM_OK;
+}
+
+int engine_window_end(otm_engine* E, std::string* err) {
+  if (!E->win_open) {
+    *err = "no window is open on this engine";
+    return OTM_EINVAL;
+  }
+  for (otm_engine* M : window_members(E)) window_drop(M);
+  E->win_open = false;
+  return OTM_OK;
+}
+
+int engine_window_flush(otm_engine* E, char** body, size_t* body_len, int64_t* n_records, std::string* err) {
+  if (!E->win_open) {
+    *err = "no window is open on this engine";
+    return OTM_EINVAL;
+  }
+  const std::vector<otm_engine*> ms = window_members(E);
+  for (otm_engine* M : ms)
+    if (!M->win_open || !M->win_counts || !M->win_sums) {
+      *err = "a member of this engine holds no window buffers";
+      return OTM_EINVAL;
+    }
+  otm_engine* M0 = ms[0];
+  const int nbins = E->win_nbins;
+  const int64_t S = (int64_t)M0->host.h.n_segments;
+  const size_t cb = (size_t)S * (size_t)nbins * 4, sb = (size_t)S * 8;
+  // the window's batches ran on the engine's, its clones' and its members'
+  // streams (and a caller's, otm_match_device): wait for each device's work
+  for (size_t i = 0; i < ms.size(); ++i) {
+    bool seen = false;
+    for (size_t k = 0; k < i; ++k) seen = seen || ms[k]->device == ms[i]->device;
+    if (seen) continue;
+    HIPCHK(hipSetDevice(ms[i]->device));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  std::lock_guard<std::mutex> lk(M0->mu);
+  HIPCHK(hipSetDevice(M0->device));
+  hipStream_t s = M0->stream;
+  // the members' pairs into member 0's: in place on its device, by a peer copy
+  // into a scratch pair from another
+  int rc;
+  for (size_t i = 1; i < ms.size() && S > 0; ++i) {
+    otm_engine* M = ms[i];
+    const uint32_t* sc = (const uint32_t*)M->win_counts;
+    const unsigned long long* ss = (const unsigned long long*)M->win_sums;
+    if (M->device != M0->device) {
+      if ((rc = ensure(M0->win_peer_counts, cb, err))) return rc;
+      if ((rc = ensure(M0->win_peer_sums, sb, err))) return rc;
+      HIPCHK(hipMemcpyPeerAsync(M0->win_peer_counts.p, M0->device, M->win_counts, M->device, cb, s));
+      HIPCHK(hipMemcpyPeerAsync(M0->win_peer_sums.p, M0->device, M->win_sums, M->device, sb, s));
+      sc = (const uint32_t*)M0->win_peer_counts.p;
+      ss = (const unsigned long long*)M0->win_peer_sums.p;
+    }
+    launch_flush_add((uint32_t*)M0->win_counts, sc, S * nbins, (unsigned long long*)M0->win_sums, ss, S, s);
+  }
+  rc = engine_flush_body(M0, M0->win_counts, M0->win_sums, S, nbins, E->win_bin_kph, 0, 1, s, body, body_len,
+                         n_records, err);
+  if (rc) return rc;
+  // the window goes on from zero
+  for (otm_engine* M : ms) {
+    if (M->device != M0->device) continue;
+    HIPCHK(hipMemsetAsync(M->win_counts, 0, std::max<size_t>(cb, 16), s));
+    HIPCHK(hipMemsetAsync(M->win_sums, 0, std::max<size_t>(sb, 16), s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  for (otm_engine* M : ms) {
+    if (M->device == M0->device) continue;
+    HIPCHK(hipSetDevice(M->device));
+    HIPCHK(hipMemsetAsync(M->win_counts, 0, std::max<size_t>(cb, 16), M->stream));
+    HIPCHK(hipMemsetAsync(M->win_sums, 0, std::max<size_t>(sb, 16), M->stream));
+    HIPCHK(hipStreamSynchronize(M->stream));
+  }
   return OTM_OK;
 }
 

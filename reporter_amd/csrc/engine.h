@@ -49,6 +49,7 @@ struct otm_engine {
   // across the members by uuid and merged back (the g_* arrays hold the merged
   // results of its last batch)
   std::vector<otm_engine*> members;
+  const otm_engine* group = nullptr;  // the multi-device engine this one is a member of (its windows are the group's)
   // one persistent host thread per member (group.cpp): a HIP host thread keeps
   // runtime state that a thread spawned per batch would leak
   struct MemberPool* member_pool = nullptr;
@@ -161,6 +162,23 @@ struct otm_engine {
   // lengths, the dense blob, and its pinned host copy with offsets and flags
   Buf resp_hdr, resp_seg, resp_rep, resp_hlen, resp_slen, resp_rlen, resp_blen, resp_host, resp_blob;
   Buf h_resp, h_resp_meta;
+  // the datastore flush body written on the GPU (engine_flush_body, flush.hip):
+  // the rows' slots and lengths, the dense blob, the call's counters, and the
+  // blob's page-locked host copy; kept at the size they grew to
+  Buf flush_slots, flush_len, flush_blob, flush_meta;
+  Buf h_flush, h_flush_meta;
+  // an engine-owned window (otm_window_begin, on a parent engine or on each
+  // member of a multi-device engine): library-owned counts and speed sums,
+  // bound as otm_hist_bind_ex binds a caller's.  On a multi-device engine
+  // win_open / win_nbins / win_bin_kph describe the members' windows, and
+  // win_peer_* (member 0) receive a member's pair from another device.
+  std::mutex win_mu;  // one window call at a time (abi.cpp)
+  bool win_open = false;
+  int win_nbins = 0;
+  float win_bin_kph = 0.0f;
+  void* win_counts = nullptr;
+  void* win_sums = nullptr;
+  Buf win_peer_counts, win_peer_sums;
   // timing
   bool timing = false;
   hipEvent_t kev[2 * otm::KN_COUNT] = {};

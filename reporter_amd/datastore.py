@@ -50,6 +50,39 @@ def serialize(records):
     return json.dumps(records, separators=(",", ":")).encode("utf-8")
 
 
+def flush_body_host(counts, speed_sums, segment_ids, rank, world, nbins, bin_kph):
+    """serialize(flush_records(...)) written by libotmatch's host writer
+    (otm_flush_body_host): counts [rows * nbins] read as u32, speed sums [rows]
+    as u64, segment_ids u64 [n_segments].  Returns (bytes, n_records)."""
+    import ctypes as C
+
+    from . import _lib
+    from .engine import _check
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1))
+    c = c if c.dtype == np.uint32 else c.astype(np.int64).astype(np.uint32)
+    s = np.ascontiguousarray(np.asarray(speed_sums).reshape(-1))
+    s = s if s.dtype == np.uint64 else s.astype(np.int64).astype(np.uint64)
+    ids = np.ascontiguousarray(np.asarray(segment_ids, np.uint64))
+    out, n, nrec = C.c_void_p(), C.c_size_t(), C.c_int64()
+    _check(_lib.lib().otm_flush_body_host(c.ctypes.data, s.ctypes.data, ids.ctypes.data, len(ids), len(s), nbins,
+                                          bin_kph, rank, world, C.byref(out), C.byref(n), C.byref(nrec)))
+    return _lib.take(out, n.value), nrec.value
+
+
+def flush_body(engine, part, spart, rank, world, nbins, bin_kph, segment_ids=None):
+    """The flush body of a rank's slice (part, spart as reduce_histograms
+    returned them): written on the GPU when the tensors are there
+    (Engine.flush_body_device, with the engine's own copy of the ids), by the
+    host writer otherwise (a gloo run: segment_ids = synth.segment_ids(graph),
+    engine unused).  Returns (bytes, n_records)."""
+    if getattr(part, "is_cuda", False):
+        return engine.flush_body_device(part, spart, rank, world, nbins, bin_kph)
+    if segment_ids is None:
+        raise ValueError("host tensors need segment_ids (synth.segment_ids of the graph)")
+    to_np = lambda t: t.numpy() if hasattr(t, "numpy") else np.asarray(t)
+    return flush_body_host(to_np(part), to_np(spart), segment_ids, rank, world, nbins, bin_kph)
+
+
 def post(body, url=None, timeout=10.0):
     """POST a flush body to the datastore (url or env DATASTORE_URL, its
     secret_key query parameter included).  Returns the HTTP status; raises on

@@ -321,6 +321,43 @@ class Engine(object):
         sp = None if speed_sum is None or tensor is None else speed_sum.data_ptr()
         _check(lib().otm_hist_bind_ex(self.h, ptr, nbins, bin_kph, sp))
 
+    def window_begin(self, nbins, bin_kph):
+        """Open an engine-owned histogram window (otm_window_begin): counts
+        and speed sums in library-owned HBM, bound as hist_bind binds."""
+        _check(lib().otm_window_begin(self.h, nbins, bin_kph))
+
+    def window_flush(self):
+        """Close the window: (the datastore flush body as bytes, its record
+        count); the buffers are zeroed and the window goes on.  No match call
+        may be in progress on this engine, its clones or its members."""
+        out, n, nrec = C.c_void_p(), C.c_size_t(), C.c_int64()
+        _check(lib().otm_window_flush(self.h, C.byref(out), C.byref(n), C.byref(nrec)))
+        return _lib.take(out, n.value), nrec.value
+
+    def window_end(self):
+        _check(lib().otm_window_end(self.h))
+
+    def flush_body_device(self, counts, sums, rank, world, nbins, bin_kph):
+        """The flush body of a histogram slice in this GPU's HBM, written on
+        the GPU (otm_flush_body_device): counts int32 / uint32 tensor
+        [rows * nbins], sums int64 tensor [rows] (flush.reduce_histograms'
+        slices, or a whole window with world 1).  Returns (bytes, n_records)."""
+        import torch
+        rows = int(sums.numel())
+        if counts.element_size() != 4 or sums.element_size() != 8 or not counts.is_contiguous() \
+                or not sums.is_contiguous() or (nbins >= 1 and counts.numel() != rows * nbins):
+            raise ValueError("counts: 4-byte [rows * nbins], sums: 8-byte [rows], both contiguous")
+        # the tensors are ready on torch's current stream; the null stream has
+        # no handle to pass, so wait for it here
+        st = torch.cuda.current_stream(counts.device)
+        if not st.cuda_stream:
+            st.synchronize()
+        out, n, nrec = C.c_void_p(), C.c_size_t(), C.c_int64()
+        _check(lib().otm_flush_body_device(self.h, counts.data_ptr(), sums.data_ptr(), rows, nbins, bin_kph, rank, world,
+                                           C.c_void_p(st.cuda_stream) if st.cuda_stream else None, C.byref(out),
+                                           C.byref(n), C.byref(nrec)))
+        return _lib.take(out, n.value), nrec.value
+
     def graph_info(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _check(lib().otm_graph_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
