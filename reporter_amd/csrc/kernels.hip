@@ -2998,6 +2998,326 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
   }
 }
 
+// K5, one DPP row per trace (16 lanes, lane j = state j: four traces per
+// wavefront) -- the form for batches between the wave form's
+// and the grouped forms' (launch_viterbi: 8,192 to 32,767 traces).  The
+// previous column's scores never leave their registers: a DPP
+// row_newbcast hands lane i of each 16-lane row to the whole row as an operand
+// of the add, so prev[i] + T[i][j] is one VALU instruction and the serial
+// chain of a step holds no LDS access, shuffle or readlane.
+//  * a trace's per-point word (K3's byte | the point's block offset in the
+//    trace's transition stream << 8) goes into LDS once per trace; a chunk's
+//    words are read, row-uniform, ahead of its steps;
+//  * a chunk of OTM_VR_CH points' transition blocks (OTM_VR_U floats per lane)
+//    and emissions are loaded into registers one chunk ahead, in flight while
+//    the current chunk is stepped; the blocks are staged through a per-row LDS
+//    window at the chunk's start, the emissions stay in their lane; a chunk
+//    whose blocks exceed the window copies each step's block at the step;
+//  * backpointers as nibbles in LDS, a chain's end records its argmin, one
+//    lane per row walks backward at the end; outputs point-parallel.
+// DPP reads of a lane that EXEC has switched off do not return its value, so
+// the recurrence runs with every lane enabled and masks by selects: `prev` is
+// +inf in the lanes past a column's count (a source past Kq never wins), and
+// what a lane reads from the windows for such a source, for a target past Kp
+// or for an unlinked row is a transition float or +inf (the windows start as
+// +inf and are only ever staged from this batch's blocks), never a NaN.
+// A trace with more than VR_PTS points or a column of more than 16 candidates
+// goes to `rej`, for the wave form in list mode.  Same recurrence (min over i
+// in order, strict <, the fours' min tree and first-index select), tie rules
+// and chain breaks as viterbi_trace_global: bit-identical to the oracle.
+#ifndef OTM_VR_CH
+#define OTM_VR_CH 4
+#endif
+#ifndef OTM_VR_U
+#define OTM_VR_U 16
+#endif
+#ifndef OTM_VR_WAVES
+#define OTM_VR_WAVES 3
+#endif
+constexpr int VR_PTS = 128;  // points per trace
+// four sources i = I0 .. I0 + 3 of the recurrence: their window reads (issued
+// for all of a step's fours before the first is used), then the sums (the DPP
+// control is an immediate) and the running minimum
+template <int I0>
+__device__ __forceinline__ void vr_load(const float* Tm, const int Kp, float (&tv)[16]) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) tv[I0 + u] = Tm[(I0 + u) * Kp];
+}
+template <int I0>
+__device__ __forceinline__ void vr_four(const int pbits, const float (&tv)[16], float& best, int& bi) {
+  const float v0 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 0, 0xF, 0xF, false)) + tv[I0 + 0];
+  const float v1 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 1, 0xF, 0xF, false)) + tv[I0 + 1];
+  const float v2 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 2, 0xF, 0xF, false)) + tv[I0 + 2];
+  const float v3 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 3, 0xF, 0xF, false)) + tv[I0 + 3];
+  // in i order with strict <: the four's minimum, if below best, at the
+  // first u that reaches it (k_viterbi's form; costs >= +0: no NaN or -0);
+  // selects, not branches
+  const float m = fminf(fminf(v0, v1), fminf(v2, v3));
+  int fu = 3;
+  fu = v2 == m ? 2 : fu;
+  fu = v1 == m ? 1 : fu;
+  fu = v0 == m ? 0 : fu;
+  const bool lt = m < best;
+  best = lt ? m : best;
+  bi = lt ? I0 + fu : bi;
+}
+// win: the window's floats a chunk may use (<= VT; the tests force the
+// per-step path with a small one)
+__global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, DevWork w, int32_t* rej, int32_t* rej_n,
+                                                                  int win, int snap) {
+  constexpr int G = 16, NT = TB / G;
+  constexpr int CH = OTM_VR_CH, U = OTM_VR_U;
+  constexpr int VT = U * G;                    // transition floats per chunk window
+  constexpr int VTA = VT > G * G ? VT : G * G;  // (a window holds any one column pair's block)
+  constexpr int RS = VTA + G;                  // row stride: row g starts g x 16 banks on
+  static_assert(CH >= 1 && CH <= G && U >= 1, "chunk knobs");
+  // spill snapshot B (see k_viterbi)
+  if (OTM_FOLD_BOOKKEEPING && snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, 1, true);
+  if (*w.abort) return;
+  // the rows' windows, then G x G floats that stay +inf: a masked source's
+  // read (up to 255 floats past a block's start) stays inside
+  __shared__ float sT[NT * RS + G * G];
+  // a nibble per state (15: dead): [point * 8 + state / 2]
+  __shared__ __attribute__((aligned(8))) uint8_t sBp[NT][VR_PTS * G / 2];
+  // flags; after the walk: VG_CS | (state + 1) << 3
+  __shared__ __attribute__((aligned(8))) uint8_t sFl[NT][VR_PTS];
+  __shared__ uint32_t sM[NT][VR_PTS + G];      // K3's byte | (trans_off[p] - trans_off[a]) << 8; [n]: the trace's end
+  const int lane = threadIdx.x;
+  const int g = lane / G, j = lane % G, gb = g * G;
+  for (int f = lane; f < NT * RS + G * G; f += TB) sT[f] = INFINITY;
+  float* const sTg = sT + g * RS;
+  const int32_t ntr = b.n_traces;
+  for (int32_t tb0 = blockIdx.x * NT; tb0 < ntr; tb0 += gridDim.x * NT) {
+    const int32_t t = tb0 + g;
+    bool act = t < ntr;
+    int64_t a = 0, t0 = 0;
+    int n = 0;
+    if (act) {
+      a = b.trace_off[t];
+      n = (int)(b.trace_off[t + 1] - a);
+      if (w.trace_err[t] != 0) {
+        for (int pl = j; pl < n; pl += G) {
+          w.state[a + pl] = -1;
+          w.chain_start[a + pl] = 0;
+        }
+        act = false;
+      }
+      if (n <= 0) act = false;
+    }
+    // the trace's words (loads issued together, indices clamped into the
+    // trace); a trace this form cannot take goes to the wave form's list
+    bool take = act && n <= VR_PTS;
+    if (take) {
+      t0 = w.trans_off[a];
+      int vm[VR_PTS / G + 1];
+      int64_t to[VR_PTS / G + 1];
+#pragma unroll
+      for (int u = 0; u <= VR_PTS / G; ++u) {
+        const int pl = u * G + j;
+        vm[u] = w.vmeta[a + (pl < n ? pl : n - 1)];
+        to[u] = w.trans_off[a + (pl < n ? pl : n)];
+      }
+      bool wide = false;
+#pragma unroll
+      for (int u = 0; u <= VR_PTS / G; ++u) {
+        const int pl = u * G + j;
+        if (pl < n) wide = wide || ((vm[u] & 0x40) && (vm[u] & 0x3F) > G);
+        if (pl <= n) sM[g][pl] = (uint32_t)(pl < n ? vm[u] : 0) | ((uint32_t)(to[u] - t0) << 8);
+      }
+      take = ((__ballot(wide) >> gb) & 0xFFFFull) == 0ull;
+    }
+    if (act && !take) {
+      if (j == 0) rej[atomicAdd(rej_n, 1)] = t;
+      act = false;
+    }
+    if (!act) n = 0;
+    // (wave-uniform, and said so: the chunk loop is a scalar one)
+    const int nch = __builtin_amdgcn_readfirstlane((wave_max_i(n) + CH - 1) / CH);
+    for (int pl = j; pl < ((n + 3) & ~3); pl += G) sFl[g][pl] = 0;  // (the walk reads four points' flags a turn)
+    wave_sync();
+    const int nl = n > 0 ? n - 1 : 0;
+    // chunk c's float range in the trace's stream (an idle row: empty)
+    auto rng = [&](int c, int& lo, int& hi) {
+      const int p0 = c * CH < n ? c * CH : n, p1 = c * CH + CH < n ? c * CH + CH : n;
+      lo = act ? (int)(sM[g][p0] >> 8) : 0;
+      hi = act ? (int)(sM[g][p1] >> 8) : 0;
+    };
+    // raw values, indices clamped (past hi: the chunk's first float again)
+    float pT[U], pE[CH];
+    auto ld_data = [&](int c, int lo, int hi) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int f = lo + u * G + j;
+        pT[u] = w.trans[t0 + (f < hi ? f : lo)];
+      }
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        const int pl = c * CH + k < nl ? c * CH + k : nl;
+        pE[k] = j < KIN ? w.cand_em[(a + pl) * KIN + j] : w.cand_xem[(a + pl) * KX + (j - KIN)];
+      }
+    };
+    int lo_n, hi_n;
+    rng(0, lo_n, hi_n);
+    ld_data(0, lo_n, hi_n);
+    // ---- forward pass (wave-uniform step count; rows masked by selects)
+    float prev = INFINITY;
+    bool open = false;
+    int last = 0, lastK = 0;
+    auto end_chain = [&]() {
+      // argmin (value, state) over the row's lanes < lastK, ties to the lower state
+      float bv = j < lastK ? prev : INFINITY;
+      int bi = j;
+#pragma unroll
+      for (int o = G / 2; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, G);
+        const int oi = __shfl_xor(bi, o, G);
+        if (ov < bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      if (j == 0) sFl[g][last] = (uint8_t)(sFl[g][last] | VG_END | (bi << 3));
+    };
+    for (int c = 0; c < nch; ++c) {
+      // stage chunk c's blocks (a row without any: +inf, not whatever the
+      // clamped loads found), keep its emissions, read its points' words;
+      // then chunk c + 1's loads, in flight behind the steps
+      const int lo_c = lo_n, hi_c = hi_n;
+      const bool any = hi_c > lo_c;
+#pragma unroll
+      for (int u = 0; u < U; ++u) sTg[u * G + j] = any ? pT[u] : INFINITY;
+      float em_c[CH];
+      uint32_t mw[CH];
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        em_c[k] = pE[k];
+        mw[k] = sM[g][c * CH + k < nl ? c * CH + k : nl];
+      }
+      wave_sync();
+      rng(c + 1, lo_n, hi_n);
+      ld_data(c + 1, lo_n, hi_n);
+      const bool big = hi_c - lo_c > win;  // this row's chunk overflowed its window
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        const int pl = c * CH + k;
+        const int mk = (int)(mw[k] & 0xFFu);
+        const bool on = pl < n && (mk & 0x40);
+        const int Kp = mk & 0x3F;
+        const bool col = on && Kp > 0;
+        // (a linked column's previous column is the open chain's last)
+        const bool link = col && open && (mk & 0x80);
+        // the open chain ends before a column without candidates and before
+        // one that does not link to it
+        if (on && open && !link) end_chain();
+        const float em = em_c[k];
+        int tb = link ? (int)(mw[k] >> 8) - lo_c : 0;
+        if (__ballot(big && link) != 0ull) {
+          // the column's block (<= G x G floats) into the window first, so
+          // the recurrence reads LDS only
+          if (big) {
+            if (link) {
+              const int64_t src = t0 + (int64_t)(mw[k] >> 8);
+              for (int f = j; f < lastK * Kp; f += G) sTg[f] = w.trans[src + f];
+            }
+            tb = 0;
+          }
+          wave_sync();
+        }
+        bool started = false;
+        float cur = INFINITY;
+        const unsigned long long lb = __ballot(link);
+        if (lb != 0ull) {
+          // every lane runs this (see the DPP note above): an unlinked row's
+          // result, and a lane's past Kp, are dropped by the selects below
+          float best = INFINITY;
+          int bi = -1;
+          const int pbits = __float_as_int(prev);
+          const float* Tm = sTg + tb + j;
+          const int KpL = link ? Kp : 0;  // (an unlinked row reads its window's start)
+          // (wave-uniform guards skip a four that no row needs)
+          const bool g1 = __ballot(link && lastK > 4) != 0ull, g2 = __ballot(link && lastK > 8) != 0ull,
+                     g3 = __ballot(link && lastK > 12) != 0ull;
+          float tv[16];
+          vr_load<0>(Tm, KpL, tv);
+          if (g1) vr_load<4>(Tm, KpL, tv);
+          if (g2) vr_load<8>(Tm, KpL, tv);
+          if (g3) vr_load<12>(Tm, KpL, tv);
+          vr_four<0>(pbits, tv, best, bi);
+          if (g1) vr_four<4>(pbits, tv, best, bi);
+          if (g2) vr_four<8>(pbits, tv, best, bi);
+          if (g3) vr_four<12>(pbits, tv, best, bi);
+          const bool alive = link && j < Kp && bi >= 0;
+          const int nib = alive ? bi : 15;
+          // the neighbour lane's nibble by a DPP quad permute [1,0,3,2]
+          const int pair = __builtin_amdgcn_mov_dpp(nib, 0xB1, 0xF, 0xF, false);
+          if (link) {
+            cur = alive ? best + em : INFINITY;
+            if (!(j & 1)) sBp[g][pl * (G / 2) + (j >> 1)] = (uint8_t)(nib | (pair << 4));
+            if (((__ballot(alive) >> gb) & 0xFFFFull) != 0ull) started = true;
+            else end_chain();
+          }
+        }
+        // (selects, not branches: a column that continues no chain starts one)
+        if (col && j == 0) sFl[g][pl] = (uint8_t)(started ? VG_COL : (VG_COL | VG_CS));
+        cur = started ? cur : (j < Kp ? em : INFINITY);
+        prev = col ? cur : prev;
+        open = col || (open && !on);
+        last = col ? pl : last;
+        lastK = col ? Kp : lastK;
+      }
+      wave_sync();  // (the next chunk's staging overwrites the windows)
+    }
+    if (act && open) end_chain();
+    wave_sync();
+    // ---- backtrack: one lane per row walks the trace backward, four points
+    // a turn: their flags as one word and each point's 16 nibbles as one
+    // 8-byte read, none of which waits for the walk's state
+    if (j == 0) {
+      int sv = -1;
+      for (int q = ((n + 3) >> 2) - 1; q >= 0; --q) {
+        const uint32_t f4 = *(const uint32_t*)&sFl[g][q * 4];
+        unsigned long long nb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) nb[u] = *(const unsigned long long*)&sBp[g][(q * 4 + u) * (G / 2)];
+        uint32_t o4 = 0;
+#pragma unroll
+        for (int u = 3; u >= 0; --u) {
+          const uint32_t f = (f4 >> (8 * u)) & 0xFFu;
+          if (!(f & VG_COL)) continue;
+          if (f & VG_END) sv = (int)(f >> 3);
+          o4 |= ((f & VG_CS) | (uint32_t)((sv + 1) << 3)) << (8 * u);
+          if (sv >= 0) sv = (f & VG_CS) ? -1 : (int)((nb[u] >> (4 * sv)) & 15ull);
+        }
+        *(uint32_t*)&sFl[g][q * 4] = o4;
+      }
+    }
+    wave_sync();
+    // ---- outputs, point-parallel within the row (the chosen candidates'
+    // loads issued together, ahead of the stores)
+    {
+      int svs[VR_PTS / G];
+      int2 ch[VR_PTS / G];
+#pragma unroll
+      for (int u = 0; u < VR_PTS / G; ++u) {
+        const int pl = u * G + j;
+        svs[u] = pl < n ? (int)(sFl[g][pl] >> 3) - 1 : -1;
+        if (svs[u] >= 0) ch[u] = crec(w, a + pl, svs[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < VR_PTS / G; ++u) {
+        const int pl = u * G + j;
+        if (pl < n) {
+          const int64_t p = a + pl;
+          w.state[p] = svs[u];
+          w.chain_start[p] = (uint8_t)((sFl[g][pl] & VG_CS) ? 1 : 0);
+          if (svs[u] >= 0) w.chosen[p] = ch[u];
+        }
+      }
+    }
+    wave_sync();
+  }
+}
+
 // ============================================================== K6 route
 // Steps the index tier could not answer (w.overflow_list0 / counters_i32[4]):
 // the winning search again, its target label's predecessor chain as the path.
@@ -4445,8 +4765,9 @@ void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p
   mk.end(KN_TRANS_GLOBAL, s);
 }
 void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk) {
-  // the form: OTM_VIT_FORM (8, 16 or 64) for the tests; by default the
-  // grouped forms from 32,768 traces up, the wave form below:
+  // the form: OTM_VIT_FORM (4: the row form, 8, 16 or 64) for the tests; by
+  // default the grouped forms from 32,768 traces up, the row form from 8,192
+  // and the wave form below.  Why the grouped forms start that high:
   // a small batch's waves all fit the GPU at once, so its time is one wave's
   // (~100 steps of a latency-bound chain either way), while a large batch's
   // is wave rounds, which 8 traces per wave divide (round-4 A/B,
@@ -4456,7 +4777,32 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   const char* fe = std::getenv("OTM_VIT_FORM");
   const int forced = fe ? std::atoi(fe) : 0;
   constexpr int gmin = 32768;
-  const int form = forced ? forced : (b.n_traces >= gmin ? 8 : 64);
+  // the row form from 8,192 traces: below, a batch's waves are few enough per
+  // SIMD that a step's latency, not VALU issue, sets its time, and the wave
+  // form's step is the shorter one (profiles/viterbi_row/sweep.json: 61 us
+  // against 81 + 5 at 512 traces, even at 6,144, 125 against 103 + 5 at 8,192)
+  constexpr int rmin = 8192;
+  const int form = forced ? forced : (b.n_traces >= gmin ? 8 : (b.n_traces >= rmin ? 4 : 64));
+  if (form == 4) {
+    // the row form (k_viterbi_row: four traces per wave) over every trace;
+    // what it cannot take (more than VR_PTS points, a column wider than 16
+    // candidates) to the wave form, through overflow_list2 / [26] as below.
+    // OTM_VR_WIN: the window's floats a chunk may use (the tests force the
+    // per-step path with a small one)
+    const char* we = std::getenv("OTM_VR_WIN");
+    const int vt = OTM_VR_U * 16;
+    int win = we ? std::atoi(we) : vt;
+    win = win < 0 ? 0 : (win > vt ? vt : win);
+    mk.begin(KN_VITERBI, s);
+    hipLaunchKernelGGL(k_viterbi_row, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
+                       w.overflow_list2, w.counters_i32 + 26, win, 1);
+    // (sized for every trace, as a batch of long traces needs: a block whose
+    // list entries ran out exits at once)
+    hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
+                       (const int32_t*)w.overflow_list2, (const int32_t*)(w.counters_i32 + 26), 0);
+    mk.end(KN_VITERBI, s);
+    return;
+  }
   if (form == 64) {
     TIMED(KN_VITERBI, hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b,
                                          w, (const int32_t*)nullptr, (const int32_t*)nullptr, 1));
