@@ -1654,6 +1654,11 @@ __device__ __forceinline__ IdxRow src_row(const SrcRec* src, int32_t e, bool nod
   return R;
 }
 
+// a 64-bit word out of the two 32-bit halves an LDS record carries it in
+__device__ __forceinline__ unsigned long long word64(int lo, int hi) {
+  return (unsigned long long)(uint32_t)lo | (unsigned long long)(uint32_t)hi << 32;
+}
+
 // K4 index tier: S lanes per column, TB / S columns in flight per wave,
 // lanes over the column's Kq x Kp (source candidate, target candidate) pairs;
 // each pair is one probe of its source's index row (row ei, or E + from(ei)
@@ -1662,7 +1667,9 @@ __device__ __forceinline__ IdxRow src_row(const SrcRec* src, int32_t e, bool nod
 // route distance and turn units.  A column is a chain of ~5 dependent round
 // trips (point -> previous column -> candidates -> rows -> slots), so several
 // columns per wave multiply the misses in flight at the same occupancy.
-// Columns with more pairs than S loop within their group; columns the index
+// The front of the chain (column record, candidates, rows) runs per group; the
+// pairs of the wave's columns are then taken by all 64 lanes (OTM_TRANS_FLAT
+// below).  Columns the index
 // cannot answer (cost bound > the index's, a source row incomplete, more than
 // KC candidates) go to the search tiers (w.overflow_list0, count
 // w.counters_i32[4]).
@@ -1672,6 +1679,19 @@ __device__ __forceinline__ IdxRow src_row(const SrcRec* src, int32_t e, bool nod
 // then answers from the index; KC8 keeps the LDS words within 8 waves per SIMD.
 #ifndef OTM_TRANS_KC8
 #define OTM_TRANS_KC8 8
+#endif
+// The pair loop.  OTM_TRANS_FLAT=1: the pairs of the wave's NS columns are laid
+// end to end and lane L takes flat pairs L, L + 64, ...: ceil(sum / 64) probe
+// steps per wave, where each group looping over its own column (=0, the
+// earlier form, kept for A/B builds) takes as many as the wave's largest
+// column, ceil(max / S), with the smaller columns' lanes idle.  The front
+// phase stays per group; each pair's arithmetic, probes and stored float are
+// the same in both forms.
+#ifndef OTM_TRANS_FLAT
+#define OTM_TRANS_FLAT 1
+#endif
+#if OTM_TRANS_FLAT && OTM_TRANS_BATCH != 1
+#error "the flat pair loop takes one pair per lane per step (OTM_TRANS_BATCH=1)"
 #endif
 // waves per SIMD the register budget is sized for
 #ifndef OTM_TRANS_WAVES
@@ -1688,11 +1708,19 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
   __shared__ int4 tg[NS][KC];  // target: edge, offset bits, label key, -
   __shared__ int4 sr[NS][KC];  // source: edge, offset bits, remaining-length bits, end heading
   __shared__ IdxRow rq[NS][KC];
+#if OTM_TRANS_FLAT
+  // a column group's record for the flat pair loop, left by its first lane:
+  // {trans offset lo, hi, Kp | Kq << 8 | active << 16, gcv}, {bound, cq, the
+  // probed index level's slots lo, hi}
+  __shared__ int4 cr[NS][2];
+#endif
   // slot of candidate k in its column group's row: XOR-swizzled so that the
   // groups a ds_read_b128 lane group spans (MI355X_MICROARCH.md §LDS: lanes
   // {0-3,12-15,20-27}, ...) read different banks when they read the same k
   // (a 128-B row at 8 lanes per column puts groups sg and sg + 2 on the same
-  // 64 banks; at 16 lanes, every row spans all 64)
+  // 64 banks; at 16 lanes, every row spans all 64).  Kept under the flat pair
+  // loop, where a column's reads come from consecutive lanes instead: config 2
+  // 181.2 us with it, 183.6 without (profiles/trans_flat/knobs.json)
 #ifndef OTM_TRANS_SWZ
 #define OTM_TRANS_SWZ 1
 #endif
@@ -1702,6 +1730,33 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
   const DevIndex& X = w.idx;
   unsigned long long c_search = 0, c_settled = 0, c_relaxed = 0, c_trans = 0;
   const bool ordered = !LIST && (P.order_mask & ORDER_TRANS) != 0;
+  // algorithmic counts of the equivalent searches of the lane's own column
+  // group (per-lane partials, summed over the wave at the end): per distinct
+  // source (node, heading), the row's departure labels within the bound and
+  // the out-degrees of those whose edge end is within it too
+  auto count_searches = [&](int Kq, uint32_t cq, const uint4* xslot) {
+    for (int i = 0; i < Kq; ++i) {
+      const int4 Si = sr[sg][i ^ swz];
+      const int32_t ui = src_node(g, Si.x, __int_as_float(Si.y));
+      bool first = true;
+      for (int k = 0; k < i; ++k) {
+        const int4 Sk = sr[sg][k ^ swz];
+        first = first && !(src_node(g, Sk.x, __int_as_float(Sk.y)) == ui && Sk.w == Si.w);
+      }
+      if (!first) continue;
+      const IdxRow R = rq[sg][i ^ swz];
+      for (int64_t k = sl; k < (int64_t)R.cap; k += S) {
+        const uint4 slt = xslot[R.off + k];
+        if (slt.x == EMPTY || (slt.x & NODE_KEY) || idx_slot_cost(slt) > cq) continue;
+        ++c_settled;
+        if ((unsigned long long)idx_slot_cost(slt) + g.e_len64[slt.x] <= cq) {
+          const int32_t v = g.e_to[slt.x];
+          c_relaxed += (unsigned long long)(g.out_off[v + 1] - g.out_off[v]);
+        }
+      }
+      if (sl == 0) ++c_search;
+    }
+  };
   int64_t base, end, stride;
   if (LIST) {
     base = (int64_t)blockIdx.x * NS;
@@ -1820,6 +1875,97 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
       w.overflow_list0[slot] = (int32_t)p;
     }
     act = act && !spill;
+#if OTM_TRANS_FLAT
+    // an inactive group (out of range, unlinked, wide-listed, spilled) has no pairs
+    const int npair_g = act ? Kq * Kp : 0;
+    if (sl == 0) {
+      const unsigned long long xs = (unsigned long long)xslot;
+      cr[sg][0] = make_int4((int)(uint32_t)toff, (int)(uint32_t)((unsigned long long)toff >> 32),
+                            act ? (Kp | Kq << 8 | 1 << 16) : 0, __float_as_int(gcv));
+      cr[sg][1] = make_int4(__float_as_int(bound), (int)cq, (int)(uint32_t)xs, (int)(uint32_t)(xs >> 32));
+    }
+    wave_sync();
+    {
+      // the groups' pair counts (wave-uniform, from each group's first lane)
+      // and their exclusive prefix: flat pair f of the wave is pair f - pre[c]
+      // of the last column c with pre[c] <= f
+      int pre[NS], total = 0;
+#pragma unroll
+      for (int c = 0; c < NS; ++c) {
+        pre[c] = total;
+        total += __builtin_amdgcn_readlane(npair_g, c * S);
+      }
+      unsigned long long ntr = 0;
+      for (int f = lane; f < total; f += TB) {
+        int c = 0, pc = 0;
+#pragma unroll
+        for (int k = 1; k < NS; ++k) {
+          if (f >= pre[k]) {
+            c = k;
+            pc = pre[k];
+          }
+        }
+        const int idx = f - pc;
+        const int cz = !OTM_TRANS_SWZ ? 0 : (S == 8 ? ((c >> 1) & 1) * 4 : (c & 1) * 8);
+        const int4 C0 = cr[c][0], C1 = cr[c][1];
+        const int kp = C0.z & 255;
+        const float gcv_c = __int_as_float(C0.w), bound_c = __int_as_float(C1.x);
+        const uint32_t cq_c = (uint32_t)C1.y;
+        const uint4* xslot_c = (const uint4*)word64(C1.z, C1.w);
+        const int64_t toff_c = (int64_t)word64(C0.x, C0.y);
+        const int i = idx / kp, j = idx - (idx / kp) * kp;
+        const int4 T = tg[c][j ^ cz], Sx = sr[c][i ^ cz];
+        const uint32_t key = (uint32_t)T.z;
+        const int32_t ej = T.x, ei = Sx.x;
+        const float oj = __int_as_float(T.y), oi = __int_as_float(Sx.y), si = __int_as_float(Sx.z);
+        float r = 0.0f;
+        bool ok = true;
+        uint32_t units = 0;
+        if (same_edge_step(ei, oi, ej, oj)) {
+          r = same_edge_dist(oi, oj);
+        } else {
+          const IdxRow R = rq[c][i ^ cz];
+          uint4 sv = make_uint4(EMPTY, 0u, 0u, 0u);
+          if (R.cnt > 0) {
+            // the pair's bucket: two slots, one aligned 32-B piece of a line
+            uint32_t h = idx_slot0((uint32_t)T.w, R);
+            sv = xslot_c[R.off + h];
+            uint4 s1 = xslot_c[R.off + h + 1];
+            if (sv.x != key && sv.x != EMPTY) {
+              sv = s1;
+              h = h + 1u;
+              while (sv.x != key && sv.x != EMPTY) {  // the rest of the linear probe (rare)
+                h = idx_next(h, R);
+                sv = xslot_c[R.off + h];
+              }
+            }
+          }
+          // a label of the row beyond this column's cost bound is not one
+          // of its search's labels
+          if (R.cnt > 0 && sv.x == key && idx_slot_cost(sv) <= cq_c) {
+            const float sd = si + bitsf(sv.z);
+            r = sd + oj;
+            units = idx_slot_units(sv);
+          } else {
+            ok = false;
+          }
+        }
+        float cost = INFINITY;
+        if (ok && r <= bound_c) {
+          cost = trans_cost(units, r, gcv_c, P.beta);
+          ++ntr;
+        }
+        w.trans[toff_c + idx] = cost;
+      }
+      if (w.ctr) {
+        // the work counters keep their per-group form, from the group's record
+        const int4 C0 = cr[sg][0], C1 = cr[sg][1];
+        if (C0.z >> 16)
+          count_searches((C0.z >> 8) & 255, (uint32_t)C1.y, (const uint4*)word64(C1.z, C1.w));
+        c_trans += ntr;
+      }
+    }
+#else
     wave_sync();
     if (act) {
       float* Tm = w.trans + toff;
@@ -1894,34 +2040,11 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
         }
       }
       if (w.ctr) {
-        // algorithmic counts of the equivalent searches (per-lane partials,
-        // summed over the wave at the end): per distinct source (node,
-        // heading), the row's departure labels within the bound and the
-        // out-degrees of those whose edge end is within it too
-        for (int i = 0; i < Kq; ++i) {
-          const int4 Si = sr[sg][i ^ swz];
-          const int32_t ui = src_node(g, Si.x, __int_as_float(Si.y));
-          bool first = true;
-          for (int k = 0; k < i; ++k) {
-            const int4 Sk = sr[sg][k ^ swz];
-            first = first && !(src_node(g, Sk.x, __int_as_float(Sk.y)) == ui && Sk.w == Si.w);
-          }
-          if (!first) continue;
-          const IdxRow R = rq[sg][i ^ swz];
-          for (int64_t k = sl; k < (int64_t)R.cap; k += S) {
-            const uint4 slt = xslot[R.off + k];
-            if (slt.x == EMPTY || (slt.x & NODE_KEY) || idx_slot_cost(slt) > cq) continue;
-            ++c_settled;
-            if ((unsigned long long)idx_slot_cost(slt) + g.e_len64[slt.x] <= cq) {
-              const int32_t v = g.e_to[slt.x];
-              c_relaxed += (unsigned long long)(g.out_off[v + 1] - g.out_off[v]);
-            }
-          }
-          if (sl == 0) ++c_search;
-        }
+        count_searches(Kq, cq, xslot);
         c_trans += ntr;
       }
     }
+#endif
     wave_sync();
   }
   if (w.ctr) {
@@ -4611,7 +4734,10 @@ int grid_for(int64_t n, int per_block, int cap) {
 
 // ============================================================== launchers
 constexpr int WAVE_GRID_CAP = 256 * 64;  // grid-stride cap for wave kernels
-constexpr int TRANS_GRID_CAP = 65536;  // k_trans_sub waves (one per column, grid-striding beyond)
+#ifndef OTM_TRANS_GRID_CAP
+#define OTM_TRANS_GRID_CAP 65536
+#endif
+constexpr int TRANS_GRID_CAP = OTM_TRANS_GRID_CAP;  // k_trans_sub waves (one per column, grid-striding beyond)
 
 }  // namespace
 
