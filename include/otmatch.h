@@ -84,6 +84,14 @@ typedef struct otm_meili_params {
   int32_t max_candidates;
 } otm_meili_params;
 int otm_config_meili(const char* cfg_path, otm_meili_params* out);
+/* The queue threshold a config file gives, without a device:
+ * "otm":{"queue_speed_kph": v} in km/h.  Absent or 0: off (*kph = 0, every
+ * queue_length is 0 and no kernel is added to a match).  A negative,
+ * non-finite or non-numeric v is OTM_EINVAL with a message, here and in
+ * otm_engine_create, which uses exactly this.  otm_queue_info: the threshold
+ * an engine runs with (clones and members inherit it). */
+int otm_config_queue(const char* cfg_path, float* kph);
+int otm_queue_info(const otm_engine* eng, float* kph);
 /* Members of an engine: ndev of a multi-device engine, 1 otherwise. */
 int otm_engine_members(const otm_engine* eng);
 /* Member i of a multi-device engine (NULL when out of range); a one-device
@@ -232,7 +240,9 @@ typedef struct otm_segment {
   double start_time;    /* valid only if (flags & OTM_SEG_START_VALID)     */
   double end_time;      /* valid only if (flags & OTM_SEG_END_VALID)       */
   int32_t length;       /* metres, -1 if partially traversed               */
-  int32_t queue_length; /* always 0 in this era                           */
+  int32_t queue_length; /* metres from the segment's end over which the
+                           probe stayed below "queue_speed_kph" (complete
+                           OSMLR segments, DESIGN.md §3 rule 7b); 0 when off */
   int32_t begin_shape_index;
   int32_t end_shape_index;
   int32_t way_off; /* into otm_results.way_ids */
@@ -538,7 +548,8 @@ int otm_get_spill_stats(otm_engine* eng, otm_spill_stats* out);
  * 6 state i32[P], 7 col_prev i32[P], 8 route_dist f32[P], 9 gc f32[P],
  * 10 ipos f32[P]; the batch inputs as the GPU request reader decoded them
  * (otm_report_batch; also a host batch of more than 2^18 points): 11 trace_off
- * i64[T+1], 12 lat f32[P], 13 lon f32[P], 14 time f64[P], 15 accuracy f32[P]. */
+ * i64[T+1], 12 lat f32[P], 13 lon f32[P], 14 time f64[P], 15 accuracy f32[P];
+ * 16 chain_start u8[P], 17 is_col u8[P]. */
 int otm_debug_fetch(otm_engine* eng, int what, void* dst, size_t bytes,
                     size_t* needed);
 int otm_kmax(void);

@@ -88,6 +88,9 @@ public final class OtmMatcher {
   // int otm_window_end(otm_engine*)
   private static final MethodHandle WINDOW_END = fn("otm_window_end",
       FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS));
+  // int otm_queue_info(const otm_engine*, float* kph)
+  private static final MethodHandle QUEUE_INFO = fn("otm_queue_info",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS));
 
   // otm_result: {uint64_t tag; int code; (4 bytes padding) char* body; size_t body_len} = 32 bytes
   private static final MemoryLayout RESULT = MemoryLayout.structLayout(ValueLayout.JAVA_LONG.withName("tag"),
@@ -208,6 +211,17 @@ public final class OtmMatcher {
       byte[] v = p.reinterpret(len.get(ValueLayout.JAVA_LONG, 0)).toArray(ValueLayout.JAVA_BYTE);
       FREE.invokeExact(p);
       return v;
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /** The queue threshold the engine runs with, km/h ("otm":{"queue_speed_kph"} of its config; 0: off). */
+  public static float queueSpeedKph() {
+    try (Arena a = Arena.ofConfined()) {
+      MemorySegment kph = a.allocate(ValueLayout.JAVA_FLOAT);
+      check((int) QUEUE_INFO.invokeExact(ENGINE, kph), "otm_queue_info");
+      return kph.get(ValueLayout.JAVA_FLOAT, 0);
     } catch (Throwable t) {
       throw new IllegalStateException(t);
     }

@@ -134,6 +134,8 @@ def _declare(L):
         "otm_engine_create": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_int, pp]),
         "otm_engine_members": (C.c_int, [vp]),
         "otm_config_meili": (C.c_int, [C.c_char_p, vp]),
+        "otm_config_queue": (C.c_int, [C.c_char_p, C.POINTER(C.c_float)]),
+        "otm_queue_info": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

@@ -1430,6 +1430,40 @@ int otm_config_meili(const char* cfg_path, otm_meili_params* out) {
   }
 }
 
+// "otm":{"queue_speed_kph": v} (DESIGN.md §3 rule 7b): absent or 0 is off; a
+// negative, non-finite or non-numeric v is rejected
+static bool read_queue(const Value& cfg, float* kph, std::string* err) {
+  *kph = 0.0f;
+  const Value* o = cfg.get("otm");
+  const Value* q = o && o->kind == Kind::Obj ? o->get("queue_speed_kph") : nullptr;
+  if (!q) return true;
+  if (q->kind != Kind::Int && q->kind != Kind::Float) {
+    *err = "queue_speed_kph must be a number";
+    return false;
+  }
+  const float v = (float)q->num();
+  if (!std::isfinite(v) || v < 0.0f) {
+    *err = "queue_speed_kph must be finite and >= 0 (0: off)";
+    return false;
+  }
+  *kph = v;
+  return true;
+}
+
+int otm_config_queue(const char* cfg_path, float* kph) {
+  if (!cfg_path || !kph) return fail(OTM_EINVAL, "bad arguments");
+  try {
+    std::string text, perr;
+    if (!read_file(cfg_path, &text)) return fail(OTM_EINVAL, std::string("cannot read config ") + cfg_path);
+    Value cfg;
+    if (!otm::json::parse(text, &cfg, &perr)) return fail(OTM_EINVAL, "config: " + perr);
+    if (!read_queue(cfg, kph, &perr)) return fail(OTM_EINVAL, perr);
+    return OTM_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+}
+
 static int otm_engine_create_impl(const char* cfg_path, const int* devices, int ndev, otm_engine** out) {
   if (!out) return fail(OTM_EINVAL, "out is NULL");
   *out = nullptr;
@@ -1502,6 +1536,13 @@ static int otm_engine_create_impl(const char* cfg_path, const int* devices, int 
   if (E->grid_mult < 0 || E->grid_mult > 64) {
     delete E;
     return fail(OTM_EINVAL, "grid_mult must be in [0 (auto), 64]");
+  }
+  {
+    std::string qerr;
+    if (!read_queue(cfg, &E->queue_kph, &qerr)) {
+      delete E;
+      return fail(OTM_EINVAL, qerr);
+    }
   }
   const Value* tl = o->get("trans_lanes");
   if (tl && tl->kind == Kind::Int) E->trans_lanes = (int)tl->i;
@@ -2090,6 +2131,13 @@ int otm_index_info(const otm_engine* E, float* rmax, int64_t* entries, int32_t* 
   if (entries) *entries = E->index_entries;
   if (incomplete_rows) *incomplete_rows = E->index_incomplete_rows;
   if (build_ms) *build_ms = E->index_build_ms;
+  return OTM_OK;
+}
+
+int otm_queue_info(const otm_engine* E, float* kph) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (!E->members.empty()) E = E->members[0];  // every member was made from the same config
+  if (kph) *kph = E->queue_kph;
   return OTM_OK;
 }
 

@@ -434,6 +434,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->index_build_ms = P->index_build_ms;
   C->small_points = P->small_points;
   C->trans_lanes = P->trans_lanes;
+  C->queue_kph = P->queue_kph;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -980,6 +981,8 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   scan_i64(P<int64_t>(E->seg_ub), NT, E->scan_tmp.p, E->scan_tmp.cap, s);
   mk.end(KN_SEG_SCAN, s);
   launch_segments(E->g, b, w, o, true, s, mk);
+  // K7b (DESIGN.md §3 rule 7b): only with a queue threshold; outside the timing marks
+  if (E->queue_kph > 0.0f) launch_queue(b, w, o, E->queue_kph, s);
   launch_report(b, E->drc, w, o, s, mk);
   HIPCHK(hipGetLastError());
   E->last_T = NT;
@@ -1720,6 +1723,8 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
     case 13: src = E->in_lon.p; n = Pn * 4; break;
     case 14: src = E->in_time.p; n = Pn * 8; break;
     case 15: src = E->in_acc.p; n = Pn * 4; break;
+    case 16: src = E->chain_start.p; n = Pn; break;
+    case 17: src = E->is_col.p; n = Pn; break;
     default: *err = "unknown debug buffer"; return OTM_EINVAL;
   }
   if (needed) *needed = n;

@@ -73,6 +73,7 @@ struct otm_engine {
   int64_t small_points = 0;  // batches below this many points: natural order, wave-tier candidates
   int trans_lanes = 8;      // k_trans_sub lanes per column: 8 (two passes, wide columns at 16) or 16 (one pass)
   int grid_mult = 0;         // candidate grid cells = grid_mult x grid_mult of the file's (0: auto_grid_mult)
+  float queue_kph = 0.0f;    // "otm":{"queue_speed_kph"}: the queue threshold of K7b (0: off, no launch)
   int32_t grid_rows = 0, grid_cols = 0;
   int64_t grid_entries = 0;
   otm::DevIndex idx{};

@@ -377,6 +377,9 @@ void launch_route(const DevGraph& g, const DevBatch& b, const DevParams& p, DevW
                   const Marks& mk, int from = RESUME_ALL);
 void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, bool write, hipStream_t s,
                      const Marks& mk);
+// K7b: queue_length of the complete OSMLR segments launch_segments wrote, at the
+// threshold kph > 0 (DESIGN.md §3 rule 7b); no timing slot of its own
+void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s);
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);

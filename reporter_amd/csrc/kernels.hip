@@ -4316,6 +4316,113 @@ __global__ __launch_bounds__(TB, (PT <= 128 ? 4 : 2)) void k_segments(DevGraph g
   SEGP_END
 }
 
+// ============================================================== K7b queue length
+// queue_length of one complete OSMLR segment (DESIGN.md §3 rule 7b): the
+// intervals between consecutive anchors of a chain (rule 7's anchors: the
+// states, and per step the placed interpolated points not behind an earlier
+// one) whose first anchor lies in [bsi, esi], walked from the last one
+// backwards.  An interval is slow when it covers less than kph x its duration;
+// the segment's queue is the trailing run of slow intervals (after at most one
+// discharge interval), each clipped to [T0, T1] by time, summed in double in
+// walk order.  The walk ends at the first interval that is not slow, so a
+// free-flowing segment costs two intervals; a step's anchors are found by the
+// forward scan step_bound makes (the monotone filter has no backward form), so
+// a step with m interpolated points costs O(m) per anchor taken from it.
+// Every read is of the trace's own points [a, a + n).
+__device__ int32_t queue_walk(const DevBatch& b, const DevWork& w, int64_t a, int n, int bsi, int esi, double T0,
+                              double T1, int32_t length, double kph) {
+  auto is_state = [&](int pl) { return w.is_col[a + pl] && w.state[a + pl] >= 0; };
+  if (esi > n - 1) esi = n - 1;
+  if (bsi < 0) bsi = 0;
+  // the last step that can hold a first anchor: q the last state at or before esi, p the state after it
+  int q = esi;
+  while (q >= 0 && !is_state(q)) --q;
+  if (q < 0) return 0;
+  int p = q + 1;
+  while (p < n && !is_state(p)) ++p;
+  int mode = 0;  // 0: no interval yet, 1: after a discharge interval, 2: in the run
+  double sum = 0.0;
+  bool done = false;
+  while (!done && p > bsi) {
+    // q -> p is a step unless p starts a chain (or q is the trace's last state)
+    if (p < n && !w.chain_start[a + p]) {
+      int nx = p;
+      float xn = w.route_dist[a + p];
+      double tn = b.time[a + p];
+      while (nx > q) {
+        // the anchor before nx: the last point of (q, nx) at or ahead of every placed one before it, else q
+        int pv = q;
+        float xp = 0.0f;
+        for (int k = q + 1; k < nx; ++k) {
+          const float x = w.ipos[a + k];
+          if (x >= xp) {
+            xp = x;
+            pv = k;
+          }
+        }
+        const double tp = b.time[a + pv];
+        if (pv < bsi) {
+          done = true;
+          break;
+        }
+        if (pv <= esi) {
+          double d = (double)xn - (double)xp;
+          if (!(d > 0.0)) d = 0.0;
+          const double dt = tn - tp;
+          const double c = (tn < T1 ? tn : T1) - (tp > T0 ? tp : T0);
+          if (c > 0.0) {  // (then dt > 0 too)
+            const bool slow = dt > 0.0 && d * 3.6 < kph * dt;
+            const double piece = d * (c / dt);
+            if (mode == 0) {
+              sum = piece;
+              mode = slow ? 2 : 1;
+            } else if (slow) {
+              sum = sum + piece;
+              mode = 2;
+            } else {
+              done = true;
+              break;
+            }
+          }
+        }
+        nx = pv;
+        xn = xp;
+        tn = tp;
+      }
+    }
+    p = q;
+    --q;
+    while (q >= 0 && !is_state(q)) --q;
+    if (q < 0) break;
+  }
+  if (mode != 2) return 0;
+  const double r = floor(sum + 0.5);
+  return r >= (double)length ? length : (int32_t)r;
+}
+
+// One wavefront per trace, a lane per segment of the trace's region (strided
+// by the wave for a trace with more segments): each lane reads its record,
+// walks its own point range straight out of HBM (neighbouring lanes' ranges
+// are adjacent) and overwrites the record's queue_length.  Launched only with
+// a threshold; a trace with an error has no segments.
+__global__ __launch_bounds__(TB) void k_queue(DevBatch b, DevWork w, DevOut o, float kph) {
+  if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
+  const int lane = threadIdx.x;
+  for (int32_t t = blockIdx.x; t < b.n_traces; t += gridDim.x) {
+    if (w.trace_err[t] != 0) continue;
+    const int64_t a = b.trace_off[t];
+    const int n = (int)(b.trace_off[t + 1] - a);
+    const int32_t ns = o.seg_cnt[t];
+    otm_segment* SG = (otm_segment*)o.segments + (int32_t)o.seg_base[t];
+    for (int si = lane; si < ns; si += TB) {
+      const otm_segment s = SG[si];
+      if (s.segment_id < 0 || s.length < 0 || n <= 0) continue;
+      SG[si].queue_length =
+          queue_walk(b, w, a, n, s.begin_shape_index, s.end_shape_index, s.start_time, s.end_time, s.length, (double)kph);
+    }
+  }
+}
+
 // ============================================================== K8 report
 __device__ __forceinline__ bool in_lv(const int64_t* lv, int n, int64_t x) {
   for (int k = 0; k < n; ++k)
@@ -4988,6 +5095,9 @@ void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o
   hipLaunchKernelGGL((k_segments<SEGP_PTS, SEGP_TRAV>), dim3(grid_for(b.n_traces, 1, 2048)), dim3(TB), 0, s, g, b, w,
                      o, (const int32_t*)lst, (const int32_t*)cnt, (int32_t*)nullptr, (int32_t*)nullptr);
   mk.end(KN_SEG_WRITE, s);
+}
+void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s) {
+  hipLaunchKernelGGL(k_queue, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w, o, kph);
 }
 void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* tb, hipStream_t s,
                       const Marks& mk) {

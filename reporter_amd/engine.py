@@ -27,10 +27,11 @@ def _check(rc):
 
 
 def write_config(path, graph_path, index_radius_m=None, grid_mult=None, trans_lanes=None, index_near_m=None,
-                 **meili):
+                 queue_speed_kph=None, **meili):
     """Write an engine config: {"otm":{"graph":...,"index_radius_m":R},"meili":{"default":{...}}}.
     index_near_m: the near indexes' radii (a list; [] for none; default a
-    fraction of the index radius, engine.cpp build_index)."""
+    fraction of the index radius, engine.cpp build_index).
+    queue_speed_kph: the queue threshold (DESIGN.md §3 rule 7b; None or 0: off)."""
     otm = {"graph": os.path.abspath(graph_path)}
     if index_radius_m is not None:
         otm["index_radius_m"] = index_radius_m
@@ -40,6 +41,8 @@ def write_config(path, graph_path, index_radius_m=None, grid_mult=None, trans_la
         otm["grid_mult"] = grid_mult
     if trans_lanes is not None:
         otm["trans_lanes"] = trans_lanes
+    if queue_speed_kph is not None:
+        otm["queue_speed_kph"] = queue_speed_kph
     cfg = {"otm": otm, "meili": {"default": meili}}
     with open(path, "w") as f:
         json.dump(cfg, f)
@@ -121,7 +124,7 @@ class Results(object):
 
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
-                 trans_lanes=None, devices=None, index_near_m=None, **meili):
+                 trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
         with ndev > 1): traces go to member murmur2(uuid) % ndev."""
@@ -133,7 +136,8 @@ class Engine(object):
             fd, self._tmp = tempfile.mkstemp(suffix=".json", prefix="otm_cfg_")
             os.close(fd)
             config_path = write_config(self._tmp, graph_path, index_radius_m=index_radius_m, grid_mult=grid_mult,
-                                       trans_lanes=trans_lanes, index_near_m=index_near_m, **meili)
+                                       trans_lanes=trans_lanes, index_near_m=index_near_m,
+                                       queue_speed_kph=queue_speed_kph, **meili)
         h = C.c_void_p()
         devs = list(devices) if devices is not None else [device]
         dev = (C.c_int * len(devs))(*devs)
@@ -389,6 +393,12 @@ class Engine(object):
         _check(lib().otm_grid_info(self.h, C.byref(cd), C.byref(r), C.byref(c), C.byref(n), C.byref(m)))
         return {"cell_deg": cd.value, "rows": r.value, "cols": c.value, "entries": n.value, "mult": m.value}
 
+    def queue_info(self):
+        """The queue threshold in km/h (otm_queue_info; 0.0: off)."""
+        k = C.c_float()
+        _check(lib().otm_queue_info(self.h, C.byref(k)))
+        return k.value
+
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))
 
@@ -429,7 +439,8 @@ class Engine(object):
               "gc": (9, np.float32), "ipos": (10, np.float32),
               # the last batch's inputs as the GPU request reader decoded them
               "in_trace_off": (11, np.int64), "in_lat": (12, np.float32), "in_lon": (13, np.float32),
-              "in_time": (14, np.float64), "in_acc": (15, np.float32)}
+              "in_time": (14, np.float64), "in_acc": (15, np.float32),
+              "chain_start": (16, np.uint8), "is_col": (17, np.uint8)}
 
     def debug(self, name):
         what, dt = self._DEBUG[name]
