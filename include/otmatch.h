@@ -449,6 +449,78 @@ int otm_window_begin(otm_engine* eng, int nbins, float bin_kph);
 int otm_window_flush(otm_engine* eng, char** body, size_t* body_len, int64_t* n_records);
 int otm_window_end(otm_engine* eng);
 
+/* Pair windows: a second, independent kind of window.  Where the histogram
+ * window keeps one row per segment, a pair window keeps, per (time bucket,
+ * segment, next segment), the count, summed duration, summed queue_length and
+ * first / last time of the datastore reports, in a hash table in HBM that the
+ * report kernel fills as it writes the reports (errors contribute nothing; a
+ * batch redone for a capacity counts once).  The definition is
+ * reporter_amd/datastore.py's serialize(pair_records(...)):
+ *   admission   the histogram's: t1 not the int -1 of a partial next segment,
+ *               length / (t1 - t0) * 3.6 >= 0 in float64, an id of the graph;
+ *               anything else is ignored and counted nowhere
+ *   bucket      k = floor(t0 / bucket_s) - origin / bucket_s; an admitted
+ *               report with k outside [0, 4096) only adds 1 to out_of_range
+ *   key         (k, row(id), row(next_id) or none); records ascend by it, "no
+ *               next" first
+ *   body        {"mode":"auto","bucket_s":B,"origin":O,"privacy":P,"pairs":[
+ *                {"id":I,"next_id":N,"bucket":O+k*B,"count":C,"duration_ms":D,
+ *                 "length":L,"queue_length":Q,"t_min":a,"t_max":b},...]}
+ *               duration_ms the sum of int((t1 - t0) * 1000.0 + 0.5), t_min /
+ *               t_max the least floor(t0) / greatest floor(t1), "next_id"
+ *               omitted when the report had none.  All integers: no sum
+ *               depends on the order of arrival.
+ *   privacy     keys with count < privacy stay out of the body and are counted
+ *               in suppressed_keys / suppressed_reports
+ * max_keys 0 means max(65536, 8 x n_segments).  The table holds at most
+ * max_keys distinct keys (on a multi-device engine: each member's table) and
+ * does not grow: an admitted, in-range report whose key is new when the table
+ * is full adds 1 to `dropped` and nothing else -- which reports drop depends
+ * on arrival order; dropped > 0 says the window was sized too small.  HBM:
+ * 56 bytes per slot, slots the power of two >= 2 x max_keys; the flush's
+ * scratch is 304 bytes per key of max_keys (272 of them a record's slot) plus
+ * the sort's.
+ * The contract is otm_window_*'s: the binding lives on the parent engine and
+ * reaches clones at their next batch; a multi-device engine keeps one table per
+ * member on that member's device and the flush merges them on member 0's; no
+ * match call may be in progress during otm_pairs_flush; a flush clears the
+ * table and the window goes on; otm_engine_destroy ends an open pair window.
+ * A histogram window and a pair window may be open together and do not know
+ * of each other.  otm_report_segments_device does not feed a pair window.
+ * otm_pairs_add_reports runs host records (reports obtained elsewhere: another
+ * matcher, a replay) through the same device upsert: id and next_id are mapped
+ * to rows on the host, a next_id with no row counts as "no next", an id with no
+ * row is not admitted.  On a multi-device engine they go to member 0's table.
+ * otm_pairs_flush: *body NUL-terminated (the NUL not counted), released with
+ * otm_free; stats may be NULL.  otm_pairs_info: the open window's
+ * configuration (max_keys resolved) and one table's slot count.
+ * OTM_EINVAL (message in otm_last_error): a NULL cfg, bucket_s < 1,
+ * privacy < 1, origin < 0, origin % bucket_s != 0, max_keys < 0 or past 2^30
+ * (otm_pairs_cfg_check: no device, no engine); begin on a graph with more than
+ * 2^26 - 2 segments, on a clone, on a member handle, or while a pair window is
+ * open; add, flush, end or info without one. */
+typedef struct otm_pairs_cfg {
+  int32_t bucket_s;
+  int32_t privacy;
+  int64_t origin;
+  int64_t max_keys;
+} otm_pairs_cfg;
+typedef struct otm_pairs_stats {
+  int64_t reports; /* admitted and aggregated */
+  int64_t keys;
+  int64_t records;
+  int64_t suppressed_keys;
+  int64_t suppressed_reports;
+  int64_t out_of_range;
+  int64_t dropped;
+} otm_pairs_stats;
+int otm_pairs_cfg_check(const otm_pairs_cfg* cfg);
+int otm_pairs_begin(otm_engine* eng, const otm_pairs_cfg* cfg);
+int otm_pairs_add_reports(otm_engine* eng, int64_t n, const otm_report_rec* recs);
+int otm_pairs_flush(otm_engine* eng, char** body, size_t* body_len, otm_pairs_stats* stats);
+int otm_pairs_end(otm_engine* eng);
+int otm_pairs_info(const otm_engine* eng, otm_pairs_cfg* cfg, int64_t* slots);
+
 int otm_graph_info(const otm_engine* eng, int64_t* n_nodes, int64_t* n_edges,
                    int64_t* n_segments);
 

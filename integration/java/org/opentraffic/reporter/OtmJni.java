@@ -39,6 +39,17 @@ public final class OtmJni {
 
   public static native void windowEnd();
 
+  /**
+   * Pair windows (otm_pairs_begin / _flush / _end): the reports aggregated per (time bucket, segment, next
+   * segment).  pairsFlush, called between batches, returns the window's body and the window goes on empty.
+   * maxKeys 0: sized from the graph.  A failure throws IllegalStateException.
+   */
+  public static native void pairsBegin(int bucketS, long origin, int privacy, long maxKeys);
+
+  public static native byte[] pairsFlush();
+
+  public static native void pairsEnd();
+
   /** A page-locked request arena of the library (otm_request_arena_alloc) as a direct buffer. */
   private static native ByteBuffer arenaAlloc(long bytes);
 

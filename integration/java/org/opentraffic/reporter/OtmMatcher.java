@@ -88,6 +88,20 @@ public final class OtmMatcher {
   // int otm_window_end(otm_engine*)
   private static final MethodHandle WINDOW_END = fn("otm_window_end",
       FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS));
+  // int otm_pairs_begin(otm_engine*, const otm_pairs_cfg* cfg)
+  private static final MethodHandle PAIRS_BEGIN = fn("otm_pairs_begin",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS));
+  // int otm_pairs_flush(otm_engine*, char** body, size_t* body_len, otm_pairs_stats* stats)
+  private static final MethodHandle PAIRS_FLUSH = fn("otm_pairs_flush",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS, ValueLayout.ADDRESS,
+                            ValueLayout.ADDRESS));
+  // int otm_pairs_end(otm_engine*)
+  private static final MethodHandle PAIRS_END = fn("otm_pairs_end",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS));
+  // otm_pairs_cfg: {int32_t bucket_s; int32_t privacy; int64_t origin; int64_t max_keys} = 24 bytes
+  static final MemoryLayout PAIRS_CFG = MemoryLayout.structLayout(ValueLayout.JAVA_INT.withName("bucket_s"),
+      ValueLayout.JAVA_INT.withName("privacy"), ValueLayout.JAVA_LONG.withName("origin"),
+      ValueLayout.JAVA_LONG.withName("max_keys"));
   // int otm_queue_info(const otm_engine*, float* kph)
   private static final MethodHandle QUEUE_INFO = fn("otm_queue_info",
       FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS));
@@ -230,6 +244,49 @@ public final class OtmMatcher {
   public static void windowEnd() {
     try {
       check((int) WINDOW_END.invokeExact(ENGINE), "otm_window_end");
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /**
+   * Pair windows (include/otmatch.h, "Pair windows"): the datastore reports aggregated per (time bucket,
+   * segment, next segment) in a table the library keeps in device memory.  pairsBegin once (maxKeys 0: sized
+   * from the graph); pairsFlush between batches returns the window's body (compact JSON, UTF-8; keys seen by
+   * fewer than `privacy` reports left out) and the window goes on empty; pairsEnd frees it.  A histogram
+   * window may be open beside it.
+   */
+  public static void pairsBegin(int bucketS, long origin, int privacy, long maxKeys) {
+    try (Arena a = Arena.ofConfined()) {
+      MemorySegment cfg = a.allocate(PAIRS_CFG);
+      cfg.set(ValueLayout.JAVA_INT, 0, bucketS);
+      cfg.set(ValueLayout.JAVA_INT, 4, privacy);
+      cfg.set(ValueLayout.JAVA_LONG, 8, origin);
+      cfg.set(ValueLayout.JAVA_LONG, 16, maxKeys);
+      check((int) PAIRS_BEGIN.invokeExact(ENGINE, cfg), "otm_pairs_begin");
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /** The pair window's body; "pairs":[] when nothing was reported. */
+  public static byte[] pairsFlush() {
+    try (Arena a = Arena.ofConfined()) {
+      MemorySegment body = a.allocate(ValueLayout.ADDRESS);
+      MemorySegment len = a.allocate(ValueLayout.JAVA_LONG);
+      check((int) PAIRS_FLUSH.invokeExact(ENGINE, body, len, MemorySegment.NULL), "otm_pairs_flush");
+      MemorySegment p = body.get(ValueLayout.ADDRESS, 0);
+      byte[] v = p.reinterpret(len.get(ValueLayout.JAVA_LONG, 0)).toArray(ValueLayout.JAVA_BYTE);
+      FREE.invokeExact(p);
+      return v;
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  public static void pairsEnd() {
+    try {
+      check((int) PAIRS_END.invokeExact(ENGINE), "otm_pairs_end");
     } catch (Throwable t) {
       throw new IllegalStateException(t);
     }

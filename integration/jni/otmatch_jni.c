@@ -81,6 +81,34 @@ JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_windowEnd(JNIEnv* en
   if (otm_window_end(g_eng) != OTM_OK) throw_last(env);
 }
 
+/* OtmJni.pairsBegin / pairsFlush / pairsEnd: the pair window (include/otmatch.h, "Pair windows"), as the
+ * histogram window above. */
+JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_pairsBegin(JNIEnv* env, jclass c, jint bucket_s,
+                                                                       jlong origin, jint privacy, jlong max_keys) {
+  (void)c;
+  otm_pairs_cfg cfg = {(int32_t)bucket_s, (int32_t)privacy, (int64_t)origin, (int64_t)max_keys};
+  if (otm_pairs_begin(g_eng, &cfg) != OTM_OK) throw_last(env);
+}
+
+JNIEXPORT jbyteArray JNICALL Java_org_opentraffic_reporter_OtmJni_pairsFlush(JNIEnv* env, jclass c) {
+  (void)c;
+  char* body = NULL;
+  size_t n = 0;
+  if (otm_pairs_flush(g_eng, &body, &n, NULL) != OTM_OK) {
+    throw_last(env);
+    return NULL;
+  }
+  jbyteArray out = (*env)->NewByteArray(env, (jsize)n);
+  if (out) (*env)->SetByteArrayRegion(env, out, 0, (jsize)n, (const jbyte*)body);
+  otm_free(body);
+  return out;
+}
+
+JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_pairsEnd(JNIEnv* env, jclass c) {
+  (void)c;
+  if (otm_pairs_end(g_eng) != OTM_OK) throw_last(env);
+}
+
 /* OtmJni.arenaAlloc(long): a library-owned page-locked request arena (otm_request_arena_alloc) as a
  * direct ByteBuffer the Java side writes its request bytes into. */
 JNIEXPORT jobject JNICALL Java_org_opentraffic_reporter_OtmJni_arenaAlloc(JNIEnv* env, jclass c, jlong bytes) {

@@ -56,6 +56,18 @@ class SpillStats(C.Structure):
                                          "attempts", "resumed")]
 
 
+class PairsCfg(C.Structure):
+    """otm_pairs_cfg (include/otmatch.h)"""
+    _fields_ = [("bucket_s", C.c_int32), ("privacy", C.c_int32), ("origin", C.c_int64), ("max_keys", C.c_int64)]
+
+
+PAIRS_STATS = ("reports", "keys", "records", "suppressed_keys", "suppressed_reports", "out_of_range", "dropped")
+
+
+class PairsStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in PAIRS_STATS]
+
+
 class BatcherCfg(C.Structure):
     _fields_ = [("report_dist", C.c_int32), ("report_count", C.c_int32), ("report_time_s", C.c_int64),
                 ("session_gap_ms", C.c_int64), ("max_batch", C.c_int32), ("json_path", C.c_int32),
@@ -166,6 +178,12 @@ def _declare(L):
         "otm_window_begin": (C.c_int, [vp, C.c_int, C.c_float]),
         "otm_window_flush": (C.c_int, [vp, pp, psz, C.POINTER(i64)]),
         "otm_window_end": (C.c_int, [vp]),
+        "otm_pairs_cfg_check": (C.c_int, [vp]),
+        "otm_pairs_begin": (C.c_int, [vp, vp]),
+        "otm_pairs_add_reports": (C.c_int, [vp, i64, vp]),
+        "otm_pairs_flush": (C.c_int, [vp, pp, psz, vp]),
+        "otm_pairs_end": (C.c_int, [vp]),
+        "otm_pairs_info": (C.c_int, [vp, vp, C.POINTER(i64)]),
         "otm_report_segments_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), psz, C.POINTER(C.c_char_p), psz,
                                                  pp, psz, C.POINTER(C.c_int)]),
         "otm_graph_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),

@@ -2115,6 +2115,64 @@ int otm_window_end(otm_engine* E) {
   return rc ? fail(rc, err) : OTM_OK;
 }
 
+// ---- pair windows (pairs.h, engine.cpp); one window call at a time (win_mu)
+int otm_pairs_cfg_check(const otm_pairs_cfg* cfg) {
+  std::string err;
+  const int rc = otm::pairs_cfg_check(cfg, &err);
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+static const char* pairs_handle_error(const otm_engine* E) {
+  if (!E) return "engine is NULL";
+  if (E->parent) return "a pair window lives on the parent engine (clones share it)";
+  if (E->group) return "a member's pair window belongs to its multi-device engine: call it on that handle";
+  return nullptr;
+}
+
+static int pairs_call(otm_engine* E, const std::function<int(std::string*)>& f) {
+  if (const char* m = pairs_handle_error(E)) return fail(OTM_EINVAL, m);
+  std::string err;
+  int rc;
+  try {
+    std::lock_guard<std::mutex> lk(E->win_mu);
+    rc = f(&err);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_pairs_begin(otm_engine* E, const otm_pairs_cfg* cfg) {
+  return pairs_call(E, [&](std::string* err) { return otm::engine_pairs_begin(E, cfg, err); });
+}
+
+int otm_pairs_add_reports(otm_engine* E, int64_t n, const otm_report_rec* recs) {
+  return pairs_call(E, [&](std::string* err) { return otm::engine_pairs_add(E, n, recs, err); });
+}
+
+int otm_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_stats* stats) {
+  if (!body || !body_len) return fail(OTM_EINVAL, "body and body_len must not be NULL");
+  *body = nullptr;
+  *body_len = 0;
+  if (stats) *stats = otm_pairs_stats{};
+  return pairs_call(E, [&](std::string* err) { return otm::engine_pairs_flush(E, body, body_len, stats, err); });
+}
+
+int otm_pairs_end(otm_engine* E) {
+  return pairs_call(E, [&](std::string* err) { return otm::engine_pairs_end(E, err); });
+}
+
+int otm_pairs_info(const otm_engine* E, otm_pairs_cfg* cfg, int64_t* slots) {
+  if (const char* m = pairs_handle_error(E)) return fail(OTM_EINVAL, m);
+  otm_engine* W = const_cast<otm_engine*>(E);
+  std::lock_guard<std::mutex> lk(W->win_mu);
+  if (!E->pairs_open) return fail(OTM_EINVAL, "no pair window is open on this engine");
+  if (cfg) *cfg = E->pairs_cfg;
+  const otm_engine* M = E->members.empty() ? E : E->members[0];
+  if (slots) *slots = (int64_t)1 << M->pairs_tab.log2;
+  return OTM_OK;
+}
+
 int otm_graph_info(const otm_engine* E, int64_t* n_nodes, int64_t* n_edges, int64_t* n_segments) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
   if (!E->members.empty()) E = E->members[0];  // every member holds the same graph

@@ -26,6 +26,7 @@ namespace otm {
   } while (0)
 
 static int ensure(otm_engine::Buf& b, size_t bytes, std::string* err);
+static void pairs_drop(otm_engine* M);
 // host-pinned buffer of at least `bytes` (contents not kept on growth)
 static int ensure_pinned(otm_engine::Buf& b, size_t bytes, std::string* err) {
   if (bytes == 0) bytes = 16;
@@ -660,7 +661,10 @@ void engine_free(otm_engine* E) {
       &E->resp_hdr,      &E->resp_seg,     &E->resp_rep,       &E->resp_hlen,      &E->resp_slen,  &E->resp_rlen,
       &E->resp_blen,     &E->resp_host,    &E->resp_blob,
       &E->flush_slots,   &E->flush_len,    &E->flush_blob,     &E->flush_meta,     &E->win_peer_counts,
-      &E->win_peer_sums};
+      &E->win_peer_sums, &E->pairs_ckey,   &E->pairs_skey,     &E->pairs_cidx,     &E->pairs_sidx,
+      &E->pairs_sort_tmp, &E->pairs_meta,  &E->pairs_in,       &E->pm_key,         &E->pm_val,     &E->pm_ctr,
+      &E->pp_key,        &E->pp_val};
+  pairs_drop(E);
   if (E->win_counts) (void)hipFree(E->win_counts);
   if (E->win_sums) (void)hipFree(E->win_sums);
   E->win_counts = E->win_sums = nullptr;
@@ -974,6 +978,7 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     o.speed_sum = H->speed_sum;
     o.nbins = H->nbins;
     o.bin_kph = H->bin_kph;
+    o.pairs = H->pairs_tab;  // (key null: no pair window)
   }
   HIPCHK(hipMemsetAsync(E->seg_ub.p, 0, ((size_t)NT + 1) * 8, s));
   launch_seg_bound(E->g, b, dp, w, P<int64_t>(E->seg_ub), s, mk);
@@ -2028,6 +2033,335 @@ int engine_window_flush(otm_engine* E, char** body, size_t* body_len, int64_t* n
     HIPCHK(hipMemsetAsync(M->win_counts, 0, std::max<size_t>(cb, 16), M->stream));
     HIPCHK(hipMemsetAsync(M->win_sums, 0, std::max<size_t>(sb, 16), M->stream));
     HIPCHK(hipStreamSynchronize(M->stream));
+  }
+  return OTM_OK;
+}
+
+// ------------------------------------------------------------ pair windows
+// (pairs.h; the table's kernels in pairs.hip, the upsert inside k_report)
+int pairs_cfg_check(const otm_pairs_cfg* cfg, std::string* err) {
+  const char* m = nullptr;
+  if (!cfg) m = "pairs cfg is NULL";
+  else if (cfg->bucket_s < 1) m = "pairs cfg: bucket_s >= 1";
+  else if (cfg->privacy < 1) m = "pairs cfg: privacy >= 1";
+  else if (cfg->origin < 0) m = "pairs cfg: origin >= 0";
+  else if (cfg->origin % cfg->bucket_s != 0) m = "pairs cfg: origin must be a multiple of bucket_s";
+  else if (cfg->max_keys < 0) m = "pairs cfg: max_keys >= 0 (0: sized from the graph)";
+  else if (cfg->max_keys > PAIR_MAX_KEYS) m = "pairs cfg: max_keys past the table's limit (2^30)";
+  if (!m) return OTM_OK;
+  *err = m;
+  return OTM_EINVAL;
+}
+
+static int pairs_log2(int64_t max_keys) {
+  int lg = 6;  // (whole waves of slots)
+  while (((int64_t)1 << lg) < 2 * max_keys) ++lg;
+  return lg;
+}
+
+static void pairs_drop(otm_engine* M) {
+  PairTab t;
+  {
+    std::lock_guard<std::mutex> lk(M->hist_mu);
+    t = M->pairs_tab;
+    M->pairs_tab = PairTab{};
+    M->pairs_open = false;
+  }
+  if (!t.key && !t.val && !t.ctr) return;
+  (void)hipSetDevice(M->device);
+  if (t.key) (void)hipFree(t.key);  // (hipFree waits for the device's work)
+  if (t.val) (void)hipFree(t.val);
+  if (t.ctr) (void)hipFree(t.ctr);
+}
+
+static int pairs_begin_one(otm_engine* M, const otm_pairs_cfg& cfg, std::string* err) {
+  PairTab t{};
+  t.max_keys = cfg.max_keys;
+  t.origin_k = cfg.origin / cfg.bucket_s;
+  t.bucket_s = cfg.bucket_s;
+  t.log2 = pairs_log2(cfg.max_keys);
+  const size_t slots = (size_t)1 << t.log2;
+  hipError_t e = hipSetDevice(M->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&t.key, slots * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&t.val, slots * sizeof(PairVal));
+  if (e == hipSuccess) e = hipMalloc((void**)&t.ctr, 64);
+  if (e == hipSuccess) {
+    launch_pairs_clear(t, M->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(M->stream);
+  if (e != hipSuccess) {
+    if (t.key) (void)hipFree(t.key);
+    if (t.val) (void)hipFree(t.val);
+    if (t.ctr) (void)hipFree(t.ctr);
+    *err = std::string("pair table: ") + hipGetErrorString(e);
+    return OTM_EDEVICE;
+  }
+  // bound under hist_mu as the histogram is: clones read it at their next batch
+  std::lock_guard<std::mutex> lk(M->hist_mu);
+  M->pairs_tab = t;
+  M->pairs_open = true;
+  M->pairs_cfg = cfg;
+  return OTM_OK;
+}
+
+int engine_pairs_begin(otm_engine* E, const otm_pairs_cfg* cfg, std::string* err) {
+  int rc = pairs_cfg_check(cfg, err);
+  if (rc) return rc;
+  if (E->pairs_open) {
+    *err = "a pair window is already open on this engine";
+    return OTM_EINVAL;
+  }
+  const std::vector<otm_engine*> ms = window_members(E);
+  const int64_t nseg = (int64_t)ms[0]->host.h.n_segments;
+  if (nseg > PAIR_MAX_SEGMENTS) {
+    *err = "a pair window's key holds segment rows below 2^26 - 2: this graph has more segments";
+    return OTM_EINVAL;
+  }
+  otm_pairs_cfg c = *cfg;
+  if (c.max_keys == 0) c.max_keys = std::max<int64_t>(65536, 8 * nseg);
+  for (size_t i = 0; i < ms.size(); ++i) {
+    rc = pairs_begin_one(ms[i], c, err);
+    if (rc) {
+      (void)hipGetLastError();
+      for (size_t k = 0; k < i; ++k) pairs_drop(ms[k]);  // (the members this call opened)
+      return rc;
+    }
+  }
+  E->pairs_open = true;
+  E->pairs_cfg = c;
+  return OTM_OK;
+}
+
+int engine_pairs_end(otm_engine* E, std::string* err) {
+  if (!E->pairs_open) {
+    *err = "no pair window is open on this engine";
+    return OTM_EINVAL;
+  }
+  for (otm_engine* M : window_members(E)) pairs_drop(M);
+  E->pairs_open = false;
+  return OTM_OK;
+}
+
+// Host records through the device upsert (k_pairs_add): ids to rows by a
+// binary search over the graph's ids (sorted once, at the first call), the
+// records staged a chunk at a time.
+int engine_pairs_add(otm_engine* E, int64_t n, const otm_report_rec* recs, std::string* err) {
+  if (!E->pairs_open) {
+    *err = "no pair window is open on this engine";
+    return OTM_EINVAL;
+  }
+  if (n < 0 || (n > 0 && !recs)) {
+    *err = "n >= 0 and records for them";
+    return OTM_EINVAL;
+  }
+  otm_engine* M = window_members(E)[0];
+  std::lock_guard<std::mutex> lk(M->mu);
+  const int64_t nseg = (int64_t)M->host.h.n_segments;
+  if ((int64_t)M->pairs_rows.size() != nseg) {
+    M->pairs_rows.resize((size_t)nseg);
+    for (int64_t i = 0; i < nseg; ++i) M->pairs_rows[(size_t)i] = {M->host.g_id[i], (int32_t)i};
+    std::sort(M->pairs_rows.begin(), M->pairs_rows.end());
+  }
+  auto row = [&](int64_t id) -> int32_t {
+    const std::pair<uint64_t, int32_t> k{(uint64_t)id, INT32_MIN};
+    auto it = std::lower_bound(M->pairs_rows.begin(), M->pairs_rows.end(), k);
+    return it != M->pairs_rows.end() && it->first == (uint64_t)id ? it->second : -1;
+  };
+  HIPCHK(hipSetDevice(M->device));
+  hipStream_t s = M->stream;
+  constexpr int64_t CHUNK = 1 << 20;
+  std::vector<PairIn> host((size_t)std::min(n, CHUNK));
+  int rc;
+  if ((rc = ensure(M->pairs_in, host.size() * sizeof(PairIn), err))) return rc;
+  PairTab t;
+  {
+    std::lock_guard<std::mutex> hl(M->hist_mu);
+    t = M->pairs_tab;
+  }
+  for (int64_t at = 0; at < n; at += CHUNK) {
+    const int64_t m = std::min(CHUNK, n - at);
+    for (int64_t i = 0; i < m; ++i) {
+      const otm_report_rec& r = recs[at + i];
+      host[(size_t)i] = PairIn{r.t0, r.t1, row(r.id), r.next_id == -1 ? -1 : row(r.next_id), r.length,
+                               r.queue_length, r.flags, 0u};
+    }
+    HIPCHK(hipMemcpyAsync(M->pairs_in.p, host.data(), (size_t)m * sizeof(PairIn), hipMemcpyHostToDevice, s));
+    launch_pairs_add(t, (const PairIn*)M->pairs_in.p, m, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // (the staging vector and pairs_in are used again)
+  }
+  return OTM_OK;
+}
+
+// The pair window's body, written on the GPU: the occupied slots compacted,
+// sorted by key, filtered by the privacy floor and formatted one record per
+// lane, then packed and copied out as the histogram flush's records are; one
+// host sync (a second one only when the body outgrew the blob).
+int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_stats* stats, std::string* err) {
+  *body = nullptr;
+  *body_len = 0;
+  if (stats) *stats = otm_pairs_stats{};
+  if (!E->pairs_open) {
+    *err = "no pair window is open on this engine";
+    return OTM_EINVAL;
+  }
+  const std::vector<otm_engine*> ms = window_members(E);
+  for (otm_engine* M : ms)
+    if (!M->pairs_open || !M->pairs_tab.key) {
+      *err = "a member of this engine holds no pair table";
+      return OTM_EINVAL;
+    }
+  const otm_pairs_cfg cfg = E->pairs_cfg;
+  // the window's batches ran on the engine's, its clones' and its members'
+  // streams (and a caller's, otm_match_device): wait for each device's work
+  for (size_t i = 0; i < ms.size(); ++i) {
+    bool seen = false;
+    for (size_t k = 0; k < i; ++k) seen = seen || ms[k]->device == ms[i]->device;
+    if (seen) continue;
+    HIPCHK(hipSetDevice(ms[i]->device));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  otm_engine* M0 = ms[0];
+  std::lock_guard<std::mutex> lk(M0->mu);
+  HIPCHK(hipSetDevice(M0->device));
+  hipStream_t s = M0->stream;
+  int rc;
+  PairTab T = M0->pairs_tab;
+  unsigned long long hc[PAIR_C_WORDS] = {};  // a group's members' counters
+  if (ms.size() > 1) {
+    // every member's table into a scratch table on member 0's device, sized for
+    // all their keys (nothing drops); a member on another device by a peer copy
+    PairTab D = T;
+    D.max_keys = cfg.max_keys * (int64_t)ms.size();
+    D.log2 = pairs_log2(D.max_keys);
+    const size_t dslots = (size_t)1 << D.log2;
+    if ((rc = ensure(M0->pm_key, dslots * sizeof(unsigned long long), err))) return rc;
+    if ((rc = ensure(M0->pm_val, dslots * sizeof(PairVal), err))) return rc;
+    if ((rc = ensure(M0->pm_ctr, 64, err))) return rc;
+    D.key = P<unsigned long long>(M0->pm_key);
+    D.val = P<PairVal>(M0->pm_val);
+    D.ctr = P<unsigned long long>(M0->pm_ctr);
+    launch_pairs_clear(D, s);
+    for (size_t i = 0; i < ms.size(); ++i) {
+      otm_engine* M = ms[i];
+      const PairTab& S = M->pairs_tab;
+      const size_t sslots = (size_t)1 << S.log2;
+      const unsigned long long* sk = S.key;
+      const PairVal* sv = S.val;
+      if (M->device != M0->device) {
+        if ((rc = ensure(M0->pp_key, sslots * sizeof(unsigned long long), err))) return rc;
+        if ((rc = ensure(M0->pp_val, sslots * sizeof(PairVal), err))) return rc;
+        HIPCHK(hipMemcpyPeerAsync(M0->pp_key.p, M0->device, S.key, M->device, sslots * sizeof(unsigned long long), s));
+        HIPCHK(hipMemcpyPeerAsync(M0->pp_val.p, M0->device, S.val, M->device, sslots * sizeof(PairVal), s));
+        sk = P<unsigned long long>(M0->pp_key);
+        sv = P<PairVal>(M0->pp_val);
+      }
+      launch_pairs_merge(D, sk, sv, (int64_t)sslots, s);
+      // (the devices are idle: a plain copy; a group's flush is not the one-sync path)
+      unsigned long long c[PAIR_C_WORDS];
+      HIPCHK(hipMemcpy(c, S.ctr, sizeof c, hipMemcpyDeviceToHost));
+      for (int k = 0; k < PAIR_C_WORDS; ++k) hc[k] += c[k];
+    }
+    T = D;
+  }
+  const int64_t cap = T.max_keys;
+  const size_t sort_bytes = pairs_sort_tmp_bytes(cap);
+  if ((rc = ensure(M0->pairs_ckey, (size_t)cap * 8, err))) return rc;
+  if ((rc = ensure(M0->pairs_skey, (size_t)cap * 8, err))) return rc;
+  if ((rc = ensure(M0->pairs_cidx, (size_t)cap * 4, err))) return rc;
+  if ((rc = ensure(M0->pairs_sidx, (size_t)cap * 4, err))) return rc;
+  if ((rc = ensure(M0->pairs_sort_tmp, sort_bytes + 256, err))) return rc;
+  if ((rc = ensure(M0->pairs_meta, 64, err))) return rc;
+  if ((rc = ensure(M0->flush_slots, (size_t)cap * PAIR_SLOT_BYTES + 64, err))) return rc;
+  if ((rc = ensure(M0->flush_len, ((size_t)cap + 1) * 8, err))) return rc;
+  if ((rc = ensure(M0->scan_tmp, scan_tmp_bytes(cap) + 256, err))) return rc;
+  if (!M0->flush_blob.p && (rc = ensure(M0->flush_blob, (size_t)1 << 20, err))) return rc;
+  if (!M0->h_flush.p && (rc = ensure_pinned(M0->h_flush, (size_t)1 << 20, err))) return rc;
+  if ((rc = ensure_pinned(M0->h_flush_meta, 128, err))) return rc;
+  unsigned long long* ckey = P<unsigned long long>(M0->pairs_ckey);
+  PairMeta* meta = (PairMeta*)M0->pairs_meta.p;
+  unsigned long long* nocc = (unsigned long long*)((char*)M0->pairs_meta.p + sizeof(PairMeta));
+  int64_t* len = P<int64_t>(M0->flush_len);
+  char* hm = (char*)M0->h_flush_meta.p;
+  HIPCHK(hipMemsetAsync(ckey, 0xFF, (size_t)cap * 8, s));
+  HIPCHK(hipMemsetAsync(M0->pairs_meta.p, 0, 64, s));
+  launch_pairs_compact(T, ckey, P<uint32_t>(M0->pairs_cidx), nocc, s);
+  pairs_sort(ckey, P<unsigned long long>(M0->pairs_skey), P<uint32_t>(M0->pairs_cidx), P<uint32_t>(M0->pairs_sidx),
+             cap, M0->pairs_sort_tmp.p, sort_bytes, s);
+  launch_pairs_rows(T, P<unsigned long long>(M0->pairs_skey), P<uint32_t>(M0->pairs_sidx), cap, M0->g.g_id,
+                    cfg.privacy, cfg.origin, P<char>(M0->flush_slots), len, meta, s);
+  scan_i64(len, cap, M0->scan_tmp.p, M0->scan_tmp.cap, s);
+  PairMeta m{};
+  unsigned long long c0[PAIR_C_WORDS];
+  int64_t total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const int64_t bcap = (int64_t)std::min(M0->flush_blob.cap, M0->h_flush.cap) - 16;
+    launch_flush_copy(cap, PAIR_SLOT_BYTES, P<char>(M0->flush_slots), len, P<char>(M0->flush_blob), bcap, s);
+    launch_flush_out(P<char>(M0->flush_blob), len + cap, (char*)M0->h_flush.p, bcap, s);
+    if (attempt == 0) {
+      HIPCHK(hipMemcpyAsync(hm, meta, sizeof(PairMeta), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hm + 32, len + cap, 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hm + 64, T.ctr, sizeof c0, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    std::memcpy(&m, hm, sizeof m);
+    std::memcpy(&total, hm + 32, 8);
+    std::memcpy(c0, hm + 64, sizeof c0);
+    if (total <= bcap) break;
+    // the body outgrew the blob: grow both and copy again (the slots stand)
+    if ((rc = ensure(M0->flush_blob, (size_t)total + 16, err))) return rc;
+    if ((rc = ensure_pinned(M0->h_flush, (size_t)total + 16, err))) return rc;
+  }
+  // the head and tail around the records (each came with a leading comma)
+  const std::string head = "{\"mode\":\"auto\",\"bucket_s\":" + std::to_string(cfg.bucket_s) +
+                           ",\"origin\":" + std::to_string(cfg.origin) +
+                           ",\"privacy\":" + std::to_string(cfg.privacy) + ",\"pairs\":[";
+  const size_t recs = total > 0 ? (size_t)total - 1 : 0;
+  const size_t n = head.size() + recs + 2;
+  char* p = (char*)std::malloc(n + 1);
+  if (!p) {
+    *err = "out of host memory";
+    return OTM_ENOMEM;
+  }
+  std::memcpy(p, head.data(), head.size());
+  if (recs) std::memcpy(p + head.size(), (const char*)M0->h_flush.p + 1, recs);
+  std::memcpy(p + head.size() + recs, "]}", 3);
+  // the window goes on from an empty table
+  auto fail_free = [&](hipError_t e, const char* what) {
+    std::free(p);
+    *err = std::string(what) + ": " + hipGetErrorString(e);
+    return OTM_EDEVICE;
+  };
+  for (otm_engine* M : ms)
+    if (M->device == M0->device) launch_pairs_clear(M->pairs_tab, s);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail_free(e, "pair table clear");
+  for (otm_engine* M : ms) {
+    if (M->device == M0->device) continue;
+    e = hipSetDevice(M->device);
+    if (e == hipSuccess) {
+      launch_pairs_clear(M->pairs_tab, M->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(M->stream);
+    if (e != hipSuccess) return fail_free(e, "pair table clear");
+  }
+  *body = p;
+  *body_len = n;
+  if (stats) {
+    // (the flushed table's counters; with a group, the merged table's and the
+    // members'.  The reports added to keys past max_keys were dropped.)
+    const unsigned long long over = c0[PAIR_C_OVER];
+    stats->reports = (int64_t)(c0[PAIR_C_REPORTS] + hc[PAIR_C_REPORTS] - over);
+    stats->out_of_range = (int64_t)(c0[PAIR_C_RANGE] + hc[PAIR_C_RANGE]);
+    stats->dropped = (int64_t)(c0[PAIR_C_DROPPED] + hc[PAIR_C_DROPPED] + over);
+    stats->keys = (int64_t)m.keys;
+    stats->records = (int64_t)m.records;
+    stats->suppressed_keys = (int64_t)m.suppressed_keys;
+    stats->suppressed_reports = (int64_t)m.suppressed_reports;
   }
   return OTM_OK;
 }

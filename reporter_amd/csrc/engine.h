@@ -180,6 +180,20 @@ struct otm_engine {
   void* win_counts = nullptr;
   void* win_sums = nullptr;
   Buf win_peer_counts, win_peer_sums;
+  // a pair window (otm_pairs_begin, pairs.h; on a parent engine or on each
+  // member of a multi-device engine): the table in library-owned HBM, handed
+  // to every batch's DevOut under hist_mu as the histogram binding is.  On a
+  // multi-device engine pairs_open / pairs_cfg describe the members' windows.
+  // Flush scratch (the engine whose table is flushed, member 0 of a group):
+  // compacted and sorted (key, slot) pairs, the sort's scratch, the counters,
+  // the merged table of a group (pm_*), a member's table from another device
+  // (pp_*); otm_pairs_add_reports stages its records in pairs_in.
+  bool pairs_open = false;
+  otm_pairs_cfg pairs_cfg{};
+  otm::PairTab pairs_tab{};
+  Buf pairs_ckey, pairs_skey, pairs_cidx, pairs_sidx, pairs_sort_tmp, pairs_meta, pairs_in;
+  Buf pm_key, pm_val, pm_ctr, pp_key, pp_val;
+  std::vector<std::pair<uint64_t, int32_t>> pairs_rows;  // (segment id, row) ascending, built at the first add
   // timing
   bool timing = false;
   hipEvent_t kev[2 * otm::KN_COUNT] = {};

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "otmatch.h"
+#include "pairs.h"
 
 namespace otm {
 
@@ -319,6 +320,7 @@ struct DevOut {
   unsigned long long* speed_sum;  // [n_segments] sum of report speeds, 1/1000 km/h, or nullptr
   int nbins;
   float bin_kph;
+  PairTab pairs;         // the pair window's table (pairs.h); key nullptr: none
 };
 
 // Per-kernel timing (otm_get_kernel_ms): when ev != nullptr the launchers

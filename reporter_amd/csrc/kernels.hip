@@ -4563,6 +4563,31 @@ __device__ __forceinline__ void report_hist(const DevOut& o, int32_t seg_off, ot
   }
 }
 
+// The pair window's pass over one report (pairs.h), beside report_hist and
+// under its conditions: the reported segment's row, and the row of the next
+// segment when the report carries a next_id.  report_walk reports segment
+// `ps` when it reaches the first segment after it that is not internal, and
+// that segment is the next one, so it is found again from `ps` here and the
+// report's bytes stay what they were.
+__device__ __forceinline__ void report_pair(const DevOut& o, int32_t seg_off, int32_t seg_cnt, int32_t ps,
+                                            const otm_report_rec& rep) {
+  int32_t gn = -1;
+  if (rep.next_id >= 0) {
+    const otm_segment* S = (const otm_segment*)o.segments + seg_off;
+    int32_t j = ps + 1;
+    while (j < seg_cnt && (S[j].flags & OTM_SEG_INTERNAL)) ++j;
+    if (j < seg_cnt) gn = o.seg_gidx[seg_off + j];
+  }
+  pair_report(o.pairs, o.seg_gidx[seg_off + ps], gn, rep.t0, rep.t1, rep.length, rep.queue_length, rep.flags);
+}
+
+// the parallel pass over one report: the histogram, then the pair window
+__device__ __forceinline__ void report_pass(const DevOut& o, int32_t seg_off, int32_t seg_cnt, otm_report_rec& rep) {
+  const int32_t ps = (int32_t)rep.pad;
+  report_hist(o, seg_off, rep);
+  if (o.pairs.key) report_pair(o, seg_off, seg_cnt, ps, rep);
+}
+
 // report() (py/reporter_service.py:110-215), one thread per trace (the
 // OTM_REPORT_FORM 0 launch).
 __global__ __launch_bounds__(256, OTM_REPORT_WAVES) void k_report(DevBatch b, DevReportCfg rc, DevWork w, DevOut o, int32_t n_seg_total) {
@@ -4576,7 +4601,7 @@ __global__ __launch_bounds__(256, OTM_REPORT_WAVES) void k_report(DevBatch b, De
   r.rep_off = r.seg_off;
   otm_report_rec* REP = (otm_report_rec*)o.reports + r.rep_off;
   const int nrep = report_walk(t, b, rc, w, (const otm_segment*)o.segments + r.seg_off, r, REP);
-  for (int k = 0; k < nrep; ++k) report_hist(o, r.seg_off, REP[k]);
+  for (int k = 0; k < nrep; ++k) report_pass(o, r.seg_off, r.seg_cnt, REP[k]);
   r.rep_cnt = nrep;
   if (w.ctr && r.code == 200) {
     cadd(&w.ctr->segments_out, (unsigned long long)r.seg_cnt);
@@ -4627,7 +4652,7 @@ __global__ __launch_bounds__(TB) void k_report_wave(DevBatch b, DevReportCfg rc,
     }
     __syncthreads();
     const int nrep = sN;
-    for (int k = lane; k < nrep; k += TB) report_hist(o, r.seg_off, REP[k]);
+    for (int k = lane; k < nrep; k += TB) report_pass(o, r.seg_off, r.seg_cnt, REP[k]);
     __syncthreads();
   }
 }

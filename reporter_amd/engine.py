@@ -341,6 +341,37 @@ class Engine(object):
     def window_end(self):
         _check(lib().otm_window_end(self.h))
 
+    def pairs_begin(self, bucket_s, origin=0, privacy=1, max_keys=0):
+        """Open a pair window (otm_pairs_begin): the reports aggregated per
+        (time bucket, segment, next segment) in a hash table in HBM, as
+        datastore.pair_records defines.  max_keys 0: max(65536, 8 x segments)."""
+        cfg = _lib.PairsCfg(bucket_s, privacy, origin, max_keys)
+        _check(lib().otm_pairs_begin(self.h, C.byref(cfg)))
+
+    def pairs_add_reports(self, reports):
+        """Host report records (a _lib.REPORT_DTYPE array, e.g. Results.reports
+        of another matcher or a replay) into the open pair window."""
+        r = np.ascontiguousarray(reports, dtype=_lib.REPORT_DTYPE)
+        _check(lib().otm_pairs_add_reports(self.h, len(r), r.ctypes.data if len(r) else None))
+
+    def pairs_flush(self):
+        """(the pair window's body as bytes, its stats as a dict); the table is
+        cleared and the window goes on.  No match call may be in progress on
+        this engine, its clones or its members."""
+        out, n, st = C.c_void_p(), C.c_size_t(), _lib.PairsStats()
+        _check(lib().otm_pairs_flush(self.h, C.byref(out), C.byref(n), C.byref(st)))
+        return _lib.take(out, n.value), {k: getattr(st, k) for k in _lib.PAIRS_STATS}
+
+    def pairs_end(self):
+        _check(lib().otm_pairs_end(self.h))
+
+    def pairs_info(self):
+        """The open pair window: (bucket_s, origin, privacy, max_keys resolved, slots of one table)."""
+        cfg, slots = _lib.PairsCfg(), C.c_int64()
+        _check(lib().otm_pairs_info(self.h, C.byref(cfg), C.byref(slots)))
+        return {"bucket_s": cfg.bucket_s, "origin": cfg.origin, "privacy": cfg.privacy, "max_keys": cfg.max_keys,
+                "slots": slots.value}
+
     def flush_body_device(self, counts, sums, rank, world, nbins, bin_kph):
         """The flush body of a histogram slice in this GPU's HBM, written on
         the GPU (otm_flush_body_device): counts int32 / uint32 tensor
