@@ -20,11 +20,17 @@ boundaries.  Each stage therefore also reports what is *ambiguous*, from the
 reference's own values only (never from a disagreement), and the tolerances
 are functions below with their derivation.
 
-Out of scope: the placement of interpolated points on the matched route
-(`ipos`, rule 7's projection of the points between two states).  Segment
-boundaries (shape indices and times) are given only for steps with no
-interpolated point between their two states; the others are flagged unknown.
-`tests/test_interp.py` pins placement with known answers.
+Rule 7's interpolated points are covered in full: `place_point` places a point
+on its step's route (`ipos`, within tol_ipos), `Anchors` applies the monotone
+filter, and `step_boundary` gives every boundary inside a step its shape index
+(exact) and its time (within tol_time_anchored), from whichever `ipos` the
+caller passes: the reference's own (end to end) or the implementation's
+(stage-isolated).  What is ambiguous there is decided per interpolated point
+and per boundary (see those three), and excludes that point or boundary alone.
+The one thing a float64 reference cannot adjudicate is rule 7's tie between two
+pieces of equal f32 cost at different positions ("ties: earliest piece"): it
+sees such a pair as closer than its bounds and calls the point ambiguous;
+that tie stays pinned by the oracle / kernel bit-identity alone.
 
 Where the spec says "accuracy or gps_accuracy", a probe's accuracy counts when
 it is positive.
@@ -133,8 +139,55 @@ def tol_viterbi(ncols, cost, input_tol=0.0):
 def tol_time(n, dt):
     """A boundary time is t_q + dt * x / R with x <= R partial sums of the
     same n + 2 f32 terms: the quotient is within 2 (n + 4) 2^-24, the rest is
-    float64."""
+    float64.  (Steps without a placed anchor; tol_time_anchored otherwise.)"""
     return 2 * (n + 4) * U * abs(dt) + 1e-9
+
+
+def tol_cut(n, x, off_tol=0.0):
+    """Bound on |f32 x - float64 x| of a route position x = start + (the first
+    n path lengths, summed in route order): start = len - off (1), n additions
+    (n), each relative to a partial sum <= x: (n + 1) * 2^-24 * x, plus the
+    offset's own tolerance when it is not the implementation's."""
+    return (n + 1) * U * x + off_tol
+
+
+def tol_ipos(foot_tol, n, pos, off_tol=0.0):
+    """Bound on |f32 ipos - float64 ipos|, ipos = xs + (foot - o0) with xs =
+    start + (n path lengths in route order): the foot's own tolerance
+    (tol_offset; 0 for a foot that is exact, see Foot), start = len - off (1),
+    the n additions (n), the subtraction of o0 (1) and the final addition (1),
+    each relative to a quantity <= pos (every partial sum and foot - o0 are
+    parts of pos): foot_tol + (n + 3) * 2^-24 * pos, plus the tolerance of q's
+    offset (it enters start, or o0 on the first piece) when it is not the
+    implementation's."""
+    return foot_tol + (n + 3) * U * pos + off_tol
+
+
+def tol_icost(D, emis, sigma_z, pos_tol, pos, gcd, beta):
+    """Bound on a piece's cost sqdist / (2 sigma_z^2) + |pos - gc(q, k)| / beta:
+    tol_emission of the first term; the position's and gc's own bounds, the
+    subtraction and the division (2 roundings relative to |pos - gc|) over
+    beta; the final sum (1, relative to the cost)."""
+    d = abs(pos - gcd)
+    return tol_emission(D, emis, sigma_z) + (pos_tol + tol_gc(gcd) + 2 * U * d) / beta + U * (emis + d / beta)
+
+
+def tol_time_anchored(dt, den, ex, eL, eN, t=0.0):
+    """A boundary time between anchors L and N is t_L + dt * (x - x_L) / (x_N -
+    x_L), dt = t_N - t_L.  With x off by ex and the anchors by eL, eN, the
+    quotient f <= 1 is off by (ex + eL) / den + f (eL + eN) / den <= (ex + 2 eL +
+    eN) / den, den = x_N - x_L; the two f32 subtractions add 2 * 2^-24 (the
+    quotient itself and the rest are float64).  The result is capped at |dt|:
+    both values lie between t_L and t_N, because x lies between the anchors in
+    either evaluation.  Fed the implementation's own ipos, eL = eN = 0 for
+    placed anchors and only x (and R, for N = p) carries a bound.  The final
+    sum is rounded to a double of magnitude |t| once in either evaluation:
+    2 * 2^-53 * |t| on top (epoch seconds: 2.4e-7 s)."""
+    cap = abs(dt)
+    dbl = 2.0 ** -52 * abs(t)
+    if not den > 0:
+        return cap + dbl
+    return min(cap * ((ex + 2 * eL + eN) / den + 2 * U), cap) + dbl
 
 
 # ------------------------------------------------------------------ the graph file
@@ -583,32 +636,317 @@ def path_cost(chain, states):
     return float(c)
 
 
+# ------------------------------------------------------------------ rule 7: interpolated points
+class Foot(object):
+    """The closest foot of a point on an edge's polyline (brute force over its
+    shape segments, equirectangular at the point's latitude, ties to the lowest
+    shape segment): sqd, off, D (for the tolerances), tol (the offset's bound:
+    tol_offset of the winning segment, plus the spread of the offsets of the
+    segments as close within tol_sqdist when they agree -- a foot on a shared
+    vertex -- and 0 for an exact foot), amb (two segments as close within
+    tol_sqdist whose offsets differ by more than their bounds), exact0 (the
+    foot is the edge's first shape point by the clamp t = 0, decided by more
+    than the bound: its offset is 0 in any precision)."""
+    __slots__ = ("sqd", "off", "D", "tol", "amb", "exact0")
+
+
+def foot_on_edge(G, e, lat, lon):
+    s0 = int(G.eshape[e])
+    n = int(G.eshape[e + 1]) - s0 - 1
+    ls = MPD * math.cos(math.radians(lat))
+    rows = []
+    for s in range(n):
+        a, b = s0 + s, s0 + s + 1
+        ax, ay = (G.slon[a] - lon) * ls, (G.slat[a] - lat) * MPD
+        bx, by = (G.slon[b] - lon) * ls, (G.slat[b] - lat) * MPD
+        vx, vy = bx - ax, by - ay
+        l2 = vx * vx + vy * vy
+        traw = -(ax * vx + ay * vy) / l2 if l2 > 0 else 0.0
+        t = min(max(traw, 0.0), 1.0)
+        px, py = ax + t * vx, ay + t * vy
+        D = max(abs(ax), abs(ay), abs(bx), abs(by))
+        vlen = math.sqrt(l2)
+        off = min(G.scum[a] + t * (G.scum[b] - G.scum[a]), G.elen[e])
+        rows.append((px * px + py * py, s, off, D, vlen, traw))
+    sqd, s, off, D, vlen, traw = min(rows)                       # (sqd, segment): ties to the lowest segment
+    f = Foot()
+    f.sqd, f.off, f.D = sqd, off, D
+    f.tol = tol_offset(G.elen[e], D, vlen)
+    f.amb = False
+    for r in rows:
+        if r[1] != s and r[0] - sqd <= tol_sqdist(r[3]) + tol_sqdist(D):
+            if abs(r[2] - off) > tol_offset(G.elen[e], r[3], r[4]) + tol_offset(G.elen[e], D, vlen):
+                f.amb = True
+            else:
+                f.tol = max(f.tol, tol_offset(G.elen[e], r[3], r[4])) + abs(r[2] - off)
+    # t = 0 on the first shape segment by the clamp, the unclamped foot further
+    # out than the bound: offset scum[first] + 0 * (...) = 0 whatever the precision
+    f.exact0 = (not f.amb) and s == 0 and vlen > 0 and traw < 0 and -traw * vlen > f.tol and f.tol == \
+        tol_offset(G.elen[e], D, vlen)
+    if f.exact0:
+        f.tol = 0.0
+    return f
+
+
+class Piece(object):
+    """One piece of a step's route: edge, [o0, o1] on it, xs (the route
+    position of o0), nsum (path lengths summed into xs), kind ("first": the
+    rest of q's edge, "path", "last": p's edge up to its offset), cut (the index
+    of the step's cut -- the route position start + the first `cut` path
+    lengths -- where the piece begins; the first piece begins at q, cut -1)."""
+    __slots__ = ("edge", "o0", "o1", "xs", "nsum", "kind", "cut")
+
+    def __init__(self, edge, o0, o1, xs, nsum, kind, cut):
+        self.edge, self.o0, self.o1, self.xs, self.nsum, self.kind, self.cut = edge, o0, o1, xs, nsum, kind, cut
+
+
+def step_pieces(G, s, ei, oi, ej, oj):
+    """The pieces of a "route" step (rule 7): the rest of q's edge unless q is
+    a node candidate, each path edge whole, p's edge up to its offset unless p
+    is a node candidate."""
+    out = []
+    start = 0.0 if oi == 0 else G.elen[ei] - oi
+    if oi != 0:
+        out.append(Piece(ei, oi, G.elen[ei], 0.0, 0, "first", -1))
+    d = 0.0
+    for n, g in enumerate(s.path):
+        out.append(Piece(g, 0.0, G.elen[g], start + d, n, "path", n))
+        d += G.elen[g]
+    if oj != 0:
+        out.append(Piece(ej, 0.0, oj, start + d, len(s.path), "last", len(s.path)))
+    return out
+
+
+class Placed(object):
+    """An interpolated point on its step's route: pos (None: unplaced), tol
+    (tol_ipos), amb (decided by less than the bounds, see place_point), piece,
+    cut (>= 0: the position *is* that cut of the step in any precision -- the
+    foot is the first shape point of a piece that starts there, so pos = xs +
+    (0 - 0))."""
+    __slots__ = ("pos", "tol", "amb", "piece", "cut")
+
+
+def place_point(G, P, lat, lon, q, k, pieces, oi_tol=0.0, oj_tol=0.0):
+    """Rule 7's placement of point k of step q -> p on the step's pieces: per
+    piece the closest foot on the piece's edge, admissible iff its offset lies
+    inside the piece (ends included), cost sqdist / (2 sigma_z^2) + |pos -
+    gc(q, k)| / beta, the lowest cost wins, ties to the earliest piece.
+    oi_tol / oj_tol: the tolerances of q's and p's offsets when they are the
+    reference's own.
+
+    One identity: a point whose f32 (lat, lon) equal q's projects onto q's edge
+    at q's own offset (the same input through the same projection), so on the
+    first piece its foot is o0 and its position exactly 0.  (The same would
+    hold for a copy of p on p's edge, but a point between q and p lies within
+    interpolation_distance of q and p does not: there is none.)
+
+    Ambiguous, from the reference's values alone: a piece is *shaky* when its
+    foot is (Foot.amb) or when the foot's offset is within its bound of the
+    piece's o0 = off_q or o1 = off_p (an edge's own ends are no test: the
+    projection is clamped into [0, len] in any precision); the point is
+    ambiguous when a shaky piece is the winner, or could beat it within the
+    cost bounds (tol_icost), or no other piece is admissible; and when two
+    admissible pieces' costs are closer than the sum of their bounds -- unless
+    their positions agree within their bounds (the vertex two consecutive
+    pieces share: the same place either way)."""
+    la, lo = float(lat[k]), float(lon[k])
+    gcd = _gc(float(lat[q]), float(lon[q]), la, lo)
+    same_q = lat[k] == lat[q] and lon[k] == lon[q]
+    ds = 2.0 * P["sigma_z"] * P["sigma_z"]
+    rows = []                                                   # (cost, m, pos, ptol, ctol, cut, adm, shaky)
+    for m, pc in enumerate(pieces):
+        f = foot_on_edge(G, pc.edge, la, lo)
+        off, ftol, shaky = f.off, f.tol, f.amb
+        ident = same_q and pc.kind == "first"
+        if ident:
+            off, ftol, shaky = pc.o0, 0.0, False
+        else:
+            if pc.kind == "first" and abs(off - pc.o0) <= ftol + oi_tol:
+                shaky = True
+            if pc.kind == "last" and abs(off - pc.o1) <= ftol + oj_tol:
+                shaky = True
+        adm = pc.o0 <= off <= pc.o1
+        pos = pc.xs + (off - pc.o0)
+        ptol = 0.0 if ident else tol_ipos(ftol, pc.nsum, abs(pos), oi_tol)
+        emis = f.sqd / ds
+        cost = emis + abs(pos - gcd) / P["beta"]
+        ctol = tol_icost(f.D, emis, P["sigma_z"], ptol, pos, gcd, P["beta"])
+        cut = pc.cut if (f.exact0 and pc.kind != "first" and pc.o0 == 0.0 and not ident) else -1
+        rows.append((cost, m, pos, ptol, ctol, cut, adm, shaky))
+    out = Placed()
+    out.pos, out.tol, out.amb, out.piece, out.cut = None, 0.0, False, -1, -1
+    firm = [r for r in rows if r[6]]
+    best = min(firm) if firm else None                          # (cost, piece): ties to the earliest piece
+    for r in rows:
+        if r[7] and (best is None or r is best or r[0] - r[4] <= best[0] + best[4]):
+            out.amb = True
+    if best is None:
+        return out
+    out.pos, out.tol, out.piece, out.cut = best[2], best[3], best[1], best[5]
+    for r in firm:
+        if r is not best and r[0] - best[0] <= r[4] + best[4]:
+            if abs(r[2] - best[2]) <= r[3] + best[3]:
+                out.tol = max(out.tol, r[3]) + abs(r[2] - best[2])
+                if r[5] != best[5]:
+                    out.cut = -1
+            else:
+                out.amb = True
+    return out
+
+
+class Placements(object):
+    """Rule 7's placement over a batch: pos (float64[P], -1 unplaced), tol,
+    amb, cut (int, -1 none), piece (-1 none), in_step (bool: an interpolated
+    point strictly inside a "route" step of a chain)."""
+
+    def __init__(self, n):
+        self.pos, self.tol = np.full(n, -1.0), np.zeros(n)
+        self.amb, self.in_step = np.zeros(n, bool), np.zeros(n, bool)
+        self.cut, self.piece = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+
+
+def placements(G, P, batch, chains, cand_edge, cand_off, off_tol=None):
+    """chains: per trace a list of (cols, states).  off_tol: per slot (flat)
+    when the offsets are the reference's own, None when the implementation's.
+    A same-edge step (forward or a stay) places nothing; a step into a chain
+    start does not exist (chains are given apart); points after a chain's last
+    state, before its first, or in a trace without a chain stay unplaced."""
+    lat = np.asarray(batch["lat"], np.float32).astype(np.float64)
+    lon = np.asarray(batch["lon"], np.float32).astype(np.float64)
+    Utab = _utab(G, P)
+    pl = Placements(len(lat))
+    for chs in chains:
+        for cols, states in chs:
+            for c in range(1, len(cols)):
+                q, p = int(cols[c - 1]), int(cols[c])
+                if p - q < 2:
+                    continue
+                a, b = q * KMAX + states[c - 1], p * KMAX + states[c]
+                ei, oi, ej, oj = int(cand_edge[a]), float(cand_off[a]), int(cand_edge[b]), float(cand_off[b])
+                s = step(G, Utab, ei, oi, ej, oj)
+                assert s.kind is not None, "chosen states without a route"
+                if s.kind != "route":
+                    continue
+                pcs = step_pieces(G, s, ei, oi, ej, oj)
+                ti = 0.0 if off_tol is None or oi == 0 else float(off_tol[a])
+                tj = 0.0 if off_tol is None or oj == 0 else float(off_tol[b])
+                for k in range(q + 1, p):
+                    r = place_point(G, P, lat, lon, q, k, pcs, ti, tj)
+                    pl.in_step[k], pl.amb[k], pl.tol[k], pl.cut[k], pl.piece[k] = True, r.amb, r.tol, r.cut, r.piece
+                    if r.pos is not None:
+                        pl.pos[k] = r.pos
+    return pl
+
+
+class Anchors(object):
+    """A step's anchors (rule 7): q at 0, the placed points not behind an
+    earlier anchor (position >= the running maximum, in trace order), p at R.
+    pts: [(point, position, tolerance, cut)] from q on, p not included; amb:
+    a point of the step is ambiguous in its placement, or its position is
+    within the bounds of the running maximum (the filter is undecided), and
+    then every boundary of the step is; dropped: placed points the filter
+    removed.  Two points with bit-equal f32 (lat, lon) have the same position
+    in any precision (the same input through the same projection), so a copy
+    of the anchor that set the maximum is an anchor and not ambiguous."""
+
+    def __init__(self, q, p, pos, tol, amb, cut, lat, lon):
+        self.pts, self.amb, self.dropped = [(q, 0.0, 0.0, -1)], False, 0
+        run, rtol, rk = 0.0, 0.0, q
+        for k in range(q + 1, p):
+            if amb is not None and amb[k]:
+                self.amb = True
+            v = float(pos[k])
+            if not v >= 0.0:
+                continue
+            tv = 0.0 if tol is None else float(tol[k])
+            copy = rk != q and lat[k] == lat[rk] and lon[k] == lon[rk]
+            if copy:
+                v = run
+            elif tv + rtol > 0 and abs(v - run) <= tv + rtol:
+                self.amb = True
+            if v >= run:
+                self.pts.append((k, v, tv, -1 if cut is None else int(cut[k])))
+                run, rtol, rk = v, tv, k
+            else:
+                self.dropped += 1
+
+
+def step_boundary(times, an, q, p, R, R_tol, x, x_tol, cut, at_end):
+    """The boundary at route position x (the step's cut number `cut`) of step
+    q -> p with anchors `an`: -> (time, shape point, not ambiguous, time bound).
+    Shape index: the last anchor at or before x, p itself when x >= R (at_end:
+    x is R by construction -- p a node candidate and x the end of the last path
+    edge, the same f32 sum).  Time: linear between that anchor and the next
+    (tol_time_anchored), the anchor's own time when the two coincide.
+    Ambiguous: the step is (Anchors.amb); an anchor's position is within the
+    bounds of x -- unless it is x by construction (Placed.cut); R within the
+    bounds of x when not at_end."""
+    amb = an.amb
+    L = 0
+    for i, (k, v, tv, c) in enumerate(an.pts):
+        if i == 0:
+            continue
+        if c == cut and c >= 0:
+            L = i                                               # at x in any precision: at or before it
+            continue
+        if abs(v - x) <= tv + x_tol:
+            amb = True
+        if v <= x:
+            L = i
+    kL, xL, eL, _ = an.pts[L]                                   # positions are nondecreasing: a prefix
+    if L + 1 < len(an.pts):
+        kN, xN, eN, _ = an.pts[L + 1]
+    else:
+        kN, xN, eN = p, R, R_tol
+    if not at_end and abs(R - x) <= R_tol + x_tol:
+        amb = True
+    sh = p if (at_end or R <= x) else kL
+    dt = times[kN] - times[kL]
+    den = xN - xL
+    tm = times[kL] + dt * ((x - xL) / den) if den > 0 else times[kL]
+    return tm, sh, not amb, tol_time_anchored(dt, den, x_tol, eL, eN, tm)
+
+
 # ------------------------------------------------------------------ rules 6 and 7
 class Seg(object):
     """One matched segment.  segment_id None without association; start_time /
-    end_time None when not valid; the *_known flags are False where the value
-    depends on an interpolated point's placement (out of scope)."""
+    end_time None when not valid; the *_known flags are False where the
+    boundary is ambiguous (step_boundary); begin_tol / end_tol: the time
+    bounds; begin_in / end_in: 0, or the boundary lies inside a step with
+    interpolated points: 1 none of them an anchor (the two-state rule), 2 the
+    step has anchors (tol_time_anchored)."""
     __slots__ = ("segment_id", "internal", "length", "way_ids", "start_valid", "end_valid", "start_time",
-                 "end_time", "begin_shape_index", "end_shape_index", "begin_known", "end_known", "t_tol")
+                 "end_time", "begin_shape_index", "end_shape_index", "begin_known", "end_known", "begin_tol",
+                 "end_tol", "begin_in", "end_in")
 
 
-def segments_of_chain(G, P, t0, times, cols, states, cand_edge, cand_off, gc, off_tol=0.0):
+def segments_of_chain(G, P, t0, times, cols, states, cand_edge, cand_off, gc, off_tol=None, ipos=None, place=None,
+                      latlon=None):
     """cols: the chain's columns (point indices), states: their chosen slots,
-    t0: the trace's first point; off_tol: the offsets' tolerance in metres when
-    they are not the implementation's (it widens the time tolerance).  -> (segments, route_dist per column (0 for
-    the first), steps)."""
+    t0: the trace's first point; off_tol: per slot (flat) offset tolerances
+    when the offsets are not the implementation's, else None.  ipos: the
+    positions of the interpolated points (-1 unplaced) the boundaries are made
+    from -- the implementation's own (stage-isolated: exact inputs) or, when
+    None, the reference's own `place.pos` with `place.tol`; place: the
+    reference's Placements on the same states (its amb and cut flags count
+    either way); latlon: the batch's f32 (lat, lon) as float64 arrays.  ->
+    (segments, route_dist per column (0 for the first), steps, {dropped: placed
+    points the monotone filter removed, trav: traversals})."""
     Utab = _utab(G, P)
-    trav = []                                                   # [edge, off0, off1, (t, sh, known, tol) x 2]
+    # a traversal: [edge, off0, off1, begin, end], a boundary (t, sh, known, tol, inside: 0 no, 1 two-state, 2 anchored)
+    trav = []
     rdist, steps = [0.0], []
+    stats = dict(dropped=0)
     p = cols[0]
     e = int(cand_edge[p * KMAX + states[0]])
     o = float(cand_off[p * KMAX + states[0]])
-    cur = [e, o, None, (times[p], p - t0, True, 0.0), None]
+    cur = [e, o, None, (times[p], p - t0, True, 0.0, False), None]
     curmax = o
     for k in range(1, len(cols)):
         q, p = cols[k - 1], cols[k]
-        ei, oi = int(cand_edge[q * KMAX + states[k - 1]]), float(cand_off[q * KMAX + states[k - 1]])
-        ej, oj = int(cand_edge[p * KMAX + states[k]]), float(cand_off[p * KMAX + states[k]])
+        a, b = q * KMAX + states[k - 1], p * KMAX + states[k]
+        ei, oi = int(cand_edge[a]), float(cand_off[a])
+        ej, oj = int(cand_edge[b]), float(cand_off[b])
         s = step(G, Utab, ei, oi, ej, oj)
         assert s.kind is not None, "chosen states without a route"
         steps.append(s)
@@ -616,31 +954,45 @@ def segments_of_chain(G, P, t0, times, cols, states, cand_edge, cand_off, gc, of
         if s.kind != "route":
             curmax = max(curmax, oj)
             continue
-        known = p - q < 2                                       # no interpolated point inside the step
         R, n = s.r, len(s.path)
+        ti = 0.0 if off_tol is None or oi == 0 else float(off_tol[a])
+        tj = 0.0 if off_tol is None or oj == 0 else float(off_tol[b])
+        an = None
+        if p - q >= 2:                                          # interpolated points inside: the anchors decide
+            if ipos is None:
+                an = Anchors(q, p, place.pos, place.tol, place.amb, place.cut, latlon[0], latlon[1])
+            else:
+                an = Anchors(q, p, ipos, None, place.amb, place.cut, latlon[0], latlon[1])
+            stats["dropped"] += an.dropped
 
-        def bound(x):
-            tm = times[q] + (times[p] - times[q]) * (x / R) if R > 0 else times[q]
-            tt = tol_time(n, times[p] - times[q]) + (abs(times[p] - times[q]) * 2 * off_tol / R if R > 0 else 0.0)
-            return (tm, (p if R <= x else q) - t0, known, tt)
+        def bound(x, j, at_end=False):
+            if an is None or len(an.pts) == 1 and not an.amb:   # the two-state rule
+                tm = times[q] + (times[p] - times[q]) * (x / R) if R > 0 else times[q]
+                tt = tol_time(n, times[p] - times[q]) + (abs(times[p] - times[q]) * 2 * max(ti, tj) / R if R > 0
+                                                           else 0.0)
+                return (tm, (p if (at_end or R <= x) else q) - t0, True, tt, 0 if an is None else 1)
+            tm, sh, ok, tt = step_boundary(times, an, q, p, R, tol_route(n, 0.0, R, ti + tj), x,
+                                           tol_cut(j, x, ti), j, at_end)
+            return (tm, sh - t0, ok, tt, 2 if len(an.pts) > 1 else 1)
         start = 0.0 if oi == 0 else G.elen[ei] - oi
         if oi != 0:                                             # a route from a node candidate starts at its node
-            cur[2], cur[4] = G.elen[ei], bound(start)
+            cur[2], cur[4] = G.elen[ei], bound(start, 0, oj == 0 and n == 0)
             trav.append(cur)
         d = 0.0
-        for g in s.path:
+        for j, g in enumerate(s.path):
             xb = start + d
             d += G.elen[g]
-            trav.append([g, 0.0, G.elen[g], bound(xb), bound(start + d)])
-        cur = [ej, 0.0, None, bound(start + d), None]
+            trav.append([g, 0.0, G.elen[g], bound(xb, j), bound(start + d, j + 1, oj == 0 and j == n - 1)])
+        cur = [ej, 0.0, None, bound(start + d, n, oj == 0), None]
         curmax = oj
     last = cols[-1]
     if curmax != 0.0:                                           # a chain ending on a node candidate ends at the node
-        cur[2], cur[4] = curmax, (times[last], last - t0, True, 0.0)
+        cur[2], cur[4] = curmax, (times[last], last - t0, True, 0.0, False)
         trav.append(cur)
     segs = []
+    stats["trav"] = len(trav)
     if len(cols) < 2:
-        return segs, rdist, steps
+        return segs, rdist, steps, stats
     groups = []
     for k, tv in enumerate(trav):
         join = False
@@ -670,13 +1022,12 @@ def segments_of_chain(G, P, t0, times, cols, states, cand_edge, cand_off, gc, of
             s.internal = bool(G.eflags[f[0]] & INTERNAL)
         s.start_time = f[3][0] if s.start_valid else None
         s.end_time = l[4][0] if s.end_valid else None
-        s.begin_shape_index, s.begin_known = f[3][1], f[3][2]
-        s.end_shape_index, s.end_known = l[4][1], l[4][2]
-        s.t_tol = max(f[3][3], l[4][3])
+        s.begin_shape_index, s.begin_known, s.begin_tol, s.begin_in = f[3][1], f[3][2], f[3][3], f[3][4]
+        s.end_shape_index, s.end_known, s.end_tol, s.end_in = l[4][1], l[4][2], l[4][3], l[4][4]
         s.way_ids = []
         for tv in gr:
             w = int(G.eway[tv[0]])
             if not s.way_ids or s.way_ids[-1] != w:
                 s.way_ids.append(w)
         segs.append(s)
-    return segs, rdist, steps
+    return segs, rdist, steps, stats

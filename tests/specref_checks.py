@@ -12,8 +12,12 @@ Two ways, both through the same functions:
                   records, on the traces without an ambiguous decision.
 
 Every check asserts its exclusion caps (at most 5 % of traces, 1 % of
-transition entries; `max_excl=0` for hand graphs) before it compares.
-RATIOS collects the largest observed error / bound per quantity.
+transition entries, 5 % of a case's interpolated points and 5 % of its
+boundaries inside steps with interpolated points; `max_excl=0` for hand
+graphs) before it compares.  An ambiguous interpolated point or boundary
+excludes itself only, never the rest of its trace.
+RATIOS collects the largest observed error / bound per quantity, SHARES the
+excluded shares of rule 7 per (check, case).
 """
 import numpy as np
 
@@ -22,6 +26,7 @@ import specref as sr
 KMAX = sr.KMAX
 TRACE_CAP, ENTRY_CAP = 0.05, 0.01
 RATIOS = {}
+SHARES = {}
 
 
 def _ratio(name, err, bound):
@@ -36,7 +41,7 @@ class Impl(object):
 
     def __init__(self, stages, traces, segments, way_ids, npts):
         for k in ("ncand", "cand_edge", "cand_off", "cand_emis", "gc", "col_prev", "trans_off", "trans", "state",
-                  "route_dist"):
+                  "route_dist", "ipos"):
             n = {"trans_off": npts + 1, "trans": None, "cand_edge": npts * KMAX, "cand_off": npts * KMAX,
                  "cand_emis": npts * KMAX}.get(k, npts)
             setattr(self, k, np.asarray(stages[k])[:n])
@@ -53,7 +58,7 @@ class Impl(object):
     @classmethod
     def from_engine(cls, eng, res, npts):
         names = ("ncand", "cand_edge", "cand_off", "cand_emis", "gc", "col_prev", "trans_off", "trans", "state",
-                 "route_dist")
+                 "route_dist", "ipos")
         return cls({k: eng.debug(k) for k in names}, res.traces, res.segments, res.way_ids, npts)
 
     def is_col(self, batch):
@@ -137,7 +142,10 @@ class Reference(object):
                         drop.add(t)
                         self.why.setdefault(int(t), 'viterbi')
         self.dropped = drop
-        self.otol_max = float(otol.max()) if len(otol) else 0.0
+        self.otol = otol
+        # rule 7's placement on the reference's own states and offsets
+        self.place = sr.placements(G, P, batch, [[(c.cols, c.state) for c in chs] for chs in self.chains], self.ce,
+                                   self.co, off_tol=otol)
         self.fired = set()
         for c in self.cands.values():
             self.fired |= c.fired
@@ -302,6 +310,42 @@ def check_viterbi(batch, impl, max_excl=None):
     return chains
 
 
+def _latlon(batch):
+    return (np.asarray(batch["lat"], np.float32).astype(np.float64),
+            np.asarray(batch["lon"], np.float32).astype(np.float64))
+
+
+def _new_stats():
+    return dict(pts=0, pts_amb=0, placed=0, unplaced=0, dropped=0, bounds_in=0, bounds_amb=0, sh_interp=0,
+                t_anchored=0, bounds_by_trace={}, trav_by_trace={})
+
+
+def _rule7_caps(what, st, max_excl, name=None):
+    """The caps of rule 7, asserted before anything is compared."""
+    assert st["pts_amb"] <= (TRACE_CAP * st["pts"] if max_excl is None else max_excl), \
+        "%s: %d of %d interpolated points excluded as ambiguous" % (what, st["pts_amb"], st["pts"])
+    assert st["bounds_amb"] <= (TRACE_CAP * st["bounds_in"] if max_excl is None else max_excl), \
+        "%s: %d of %d boundaries inside steps with interpolated points excluded as ambiguous" % (
+            what, st["bounds_amb"], st["bounds_in"])
+    if name is not None:
+        SHARES[(what, name)] = (st["pts_amb"], st["pts"], st["bounds_amb"], st["bounds_in"])
+
+
+def _count_bounds(want, place, t, t_first, st):
+    """Counts the boundaries that are compared; per trace those inside steps
+    with interpolated points that are not ambiguous."""
+    before = st["bounds_in"] - st["bounds_amb"]
+    for w in want:
+        for inside, known, sh in ((w.begin_in, w.begin_known, w.begin_shape_index),
+                                  (w.end_in, w.end_known, w.end_shape_index)):
+            if inside:
+                st["bounds_in"] += 1
+                st["bounds_amb"] += 0 if known else 1
+                st["sh_interp"] += 1 if known and place.in_step[t_first + sh] else 0
+                st["t_anchored"] += 1 if known and inside == 2 else 0
+    st["bounds_by_trace"][t] = st["bounds_in"] - st["bounds_amb"] - before
+
+
 def _compare_segments(G, impl, t, t_first, want, what):
     tr = impl.traces[t]
     assert tr["code"] == 200, "%s: trace %d answered %d" % (what, t, tr["code"])
@@ -316,48 +360,94 @@ def _compare_segments(G, impl, t, t_first, want, what):
         assert ways == w.way_ids, at + " way_ids"
         assert bool(g["flags"] & 1) == w.start_valid and bool(g["flags"] & 2) == w.end_valid, at + " validity"
         if w.begin_known:
-            assert int(g["begin_shape_index"]) == w.begin_shape_index, at + " begin_shape_index"
+            assert int(g["begin_shape_index"]) == w.begin_shape_index, at + " begin_shape_index: %d, reference %d" % (
+                g["begin_shape_index"], w.begin_shape_index)
             if w.start_valid:
-                assert _ratio("time", abs(float(g["start_time"]) - w.start_time), w.t_tol) <= 1, at + " start_time"
+                nm = "time_anchored" if w.begin_in == 2 else "time"
+                assert _ratio(nm, abs(float(g["start_time"]) - w.start_time), w.begin_tol) <= 1, \
+                    at + " start_time %r, reference %r (bound %g)" % (float(g["start_time"]), w.start_time, w.begin_tol)
         if w.end_known:
-            assert int(g["end_shape_index"]) == w.end_shape_index, at + " end_shape_index"
+            assert int(g["end_shape_index"]) == w.end_shape_index, at + " end_shape_index: %d, reference %d" % (
+                g["end_shape_index"], w.end_shape_index)
             if w.end_valid:
-                assert _ratio("time", abs(float(g["end_time"]) - w.end_time), w.t_tol) <= 1, at + " end_time"
+                nm = "time_anchored" if w.end_in == 2 else "time"
+                assert _ratio(nm, abs(float(g["end_time"]) - w.end_time), w.end_tol) <= 1, \
+                    at + " end_time %r, reference %r (bound %g)" % (float(g["end_time"]), w.end_time, w.end_tol)
 
 
-def check_segments(G, batch, P, impl, chains):
+def check_placement(G, batch, P, impl, chains, max_excl=None, name=None):
+    """Rule 7's placement (stage-isolated A) on the implementation's own states
+    and offsets: the placed / unplaced pattern exactly and `ipos` within
+    tol_ipos for every unambiguous point; columns and points outside every
+    step are -1.  -> (the reference's Placements, statistics)."""
+    place = sr.placements(G, P, batch, [[(ch.cols, [int(impl.state[p]) for p in ch.cols]) for ch in chs]
+                                        for chs in chains], impl.cand_edge, np.asarray(impl.cand_off, np.float64))
+    st = _new_stats()
+    st["pts"], st["pts_amb"] = int(place.in_step.sum()), int((place.in_step & place.amb).sum())
+    _rule7_caps("placement", st, max_excl)
+    got = np.asarray(impl.ipos, np.float64)
+    assert (got[~place.in_step] == -1.0).all(), "a column or a point outside every step has a position"
+    for k in np.nonzero(place.in_step & ~place.amb)[0]:
+        if place.pos[k] < 0:
+            assert got[k] == -1.0, "point %d is placed at %r, the reference leaves it unplaced" % (k, got[k])
+            st["unplaced"] += 1
+        else:
+            assert got[k] >= 0.0, "point %d is unplaced, the reference places it at %r" % (k, place.pos[k])
+            assert _ratio("ipos", abs(got[k] - place.pos[k]), place.tol[k]) <= 1 or got[k] == place.pos[k], \
+                "ipos of point %d: %r, reference %r (bound %g)" % (k, got[k], place.pos[k], place.tol[k])
+            st["placed"] += 1
+    return place, st
+
+
+def check_segments(G, batch, P, impl, chains, max_excl=None, name=None):
     """Rules 6 and 7 on the implementation's own states (chains: the chain
-    structure check_viterbi returned): route distances, then the final
-    segment records."""
+    structure check_viterbi returned): route distances, rule 7's placement
+    (check_placement), then the final segment records with the boundaries
+    made from the implementation's own `ipos` (stage-isolated B)."""
     off = np.asarray(batch["trace_off"])
     times = np.asarray(batch["time"], np.float64)
     co = np.asarray(impl.cand_off, np.float64)
+    place, st = check_placement(G, batch, P, impl, chains, max_excl, name)
+    ipos, ll = np.asarray(impl.ipos, np.float64), _latlon(batch)
+    wants = []
     for t, chs in enumerate(chains):
         want = []
         for ch in chs:
-            st = [int(impl.state[p]) for p in ch.cols]
-            segs, rd, steps = sr.segments_of_chain(G, P, int(off[t]), times, ch.cols, st, impl.cand_edge, co, impl.gc)
+            sts = [int(impl.state[p]) for p in ch.cols]
+            segs, rd, steps, s7 = sr.segments_of_chain(G, P, int(off[t]), times, ch.cols, sts, impl.cand_edge, co,
+                                                      impl.gc, ipos=ipos, place=place, latlon=ll)
+            st["dropped"] += s7["dropped"]
+            st["trav_by_trace"][t] = st["trav_by_trace"].get(t, 0) + s7["trav"]
             for k in range(1, len(ch.cols)):
                 B = P["max_route_distance_factor"] * float(impl.gc[ch.cols[k]])
                 assert _ratio("route_dist", abs(float(impl.route_dist[ch.cols[k]]) - rd[k]),
                               sr.tol_route(len(steps[k - 1].path), B, rd[k])) <= 1, "route_dist at %d" % ch.cols[k]
             want += segs
+        _count_bounds(want, place, t, int(off[t]), st)
+        wants.append(want)
+    _rule7_caps("stage-isolated", st, max_excl, name)
+    for t, want in enumerate(wants):
         _compare_segments(G, impl, t, int(off[t]), want, "stage-isolated")
+    return st
 
 
-def check_isolated(G, batch, P, impl, max_excl=None):
+def check_isolated(G, batch, P, impl, max_excl=None, name=None):
+    """-> rule 7's statistics (what the case reached)."""
     check_columns(batch, P, impl, max_excl)
     check_candidates(G, batch, P, impl, max_excl)
     check_col_prev(batch, P, impl, max_excl)
     check_transitions(G, P, impl, max_excl)
     chains = check_viterbi(batch, impl, max_excl)
-    check_segments(G, batch, P, impl, chains)
+    return check_segments(G, batch, P, impl, chains, max_excl, name)
 
 
 # ---------------------------------------------------------------------- end to end
-def check_end_to_end(ref, impl, max_excl=None):
-    """The reference's own segments against the implementation's final
-    records, on the traces the reference did not exclude."""
+def check_end_to_end(ref, impl, max_excl=None, name=None):
+    """The reference's own segments, their boundaries made from its own
+    placements, against the implementation's final records, on the traces the
+    reference did not exclude; and its placements against the implementation's
+    `ipos` within tol_ipos on the same traces (its states are the
+    implementation's there).  -> rule 7's statistics."""
     G, batch, P = ref.G, ref.batch, ref.P
     ntr = len(batch["trace_off"]) - 1
     _cap("end to end", ref.dropped, ntr, TRACE_CAP, max_excl, ref.why)
@@ -365,11 +455,34 @@ def check_end_to_end(ref, impl, max_excl=None):
         "end to end: %d of %d transition entries ambiguous" % (ref.amb_entries, ref.n_entries)
     off = np.asarray(batch["trace_off"])
     times = np.asarray(batch["time"], np.float64)
+    ll, place = _latlon(batch), ref.place
+    keep = ~np.isin(_trace_of(batch), list(ref.dropped))
+    st = _new_stats()
+    st["pts"], st["pts_amb"] = int((place.in_step & keep).sum()), int((place.in_step & place.amb & keep).sum())
+    wants = {}
     for t, chs in enumerate(ref.chains):
         if t in ref.dropped:
             continue
         want = []
         for ch in chs:
-            want += sr.segments_of_chain(G, P, int(off[t]), times, ch.cols, ch.state, ref.ce, ref.co, ref.gc,
-                                         off_tol=ref.otol_max)[0]
+            segs, _, _, s7 = sr.segments_of_chain(G, P, int(off[t]), times, ch.cols, ch.state, ref.ce, ref.co, ref.gc,
+                                                  off_tol=ref.otol, place=place, latlon=ll)
+            st["dropped"] += s7["dropped"]
+            want += segs
+        _count_bounds(want, place, t, int(off[t]), st)
+        wants[t] = want
+    _rule7_caps("end to end", st, max_excl, name)
+    got = np.asarray(impl.ipos, np.float64)
+    for k in np.nonzero(place.in_step & ~place.amb & keep)[0]:
+        if place.pos[k] < 0:
+            assert got[k] == -1.0, "end to end: point %d is placed at %r, the reference leaves it unplaced" % (
+                k, got[k])
+            st["unplaced"] += 1
+        else:
+            assert got[k] >= 0.0, "end to end: point %d is unplaced, the reference places it at %r" % (k, place.pos[k])
+            assert _ratio("ipos_end_to_end", abs(got[k] - place.pos[k]), place.tol[k]) <= 1 or got[k] == place.pos[k], \
+                "end to end: ipos of point %d: %r, reference %r (bound %g)" % (k, got[k], place.pos[k], place.tol[k])
+            st["placed"] += 1
+    for t, want in wants.items():
         _compare_segments(G, impl, t, int(off[t]), want, "end to end")
+    return st
