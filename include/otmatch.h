@@ -358,6 +358,56 @@ int otm_fetch_results(otm_engine* eng, otm_results* out);
 void* otm_stream_create(otm_engine* eng, int own_queue);
 void otm_stream_destroy(void* stream);
 
+/* Matched points (extension, DESIGN.md §3 rule 7c): where on the road each
+ * input point of the last binary-level batch was put -- one record per point,
+ * in input point order, written on the GPU (k_points) after route recovery.
+ * Off by default, per handle: with the switch off a match launches and
+ * allocates nothing more.  A clone inherits its parent's value when it is
+ * made; a multi-device engine passes the call to every member.
+ *   edge/offset  a column with a state: its chosen candidate as the Viterbi
+ *                stage holds it (a node candidate in its carried form, the
+ *                node's first outgoing edge at offset 0, OTM_PT_NODE); an
+ *                interpolated point inside a route step: the piece rule 7
+ *                placed it on and its foot there (OTM_PT_ROUTE; OTM_PT_ANCHOR
+ *                when it is one of rule 7's anchors); inside a same-edge
+ *                step: its closest foot on the edge, clamped between the two
+ *                states' offsets (OTM_PT_SAME_EDGE)
+ *   lat/lon      the place on the edge's shape, interpolated in double
+ *   distance     metres from the input point to (lat, lon)
+ *   way_id       the edge's way
+ * A point without a place has edge -1 and every number 0; its flags are
+ * OTM_PT_COLUMN for a column (no candidates, no reachable state, or a trace
+ * answered 500) and 0 for an interpolated point. */
+#define OTM_PT_MATCHED 1u      /* the record has a place */
+#define OTM_PT_COLUMN 2u       /* a column of the interpolation filter (rule 1) */
+#define OTM_PT_NODE 4u         /* a node candidate */
+#define OTM_PT_CHAIN_START 8u  /* the first state of a chain */
+#define OTM_PT_ROUTE 16u       /* placed on its step's route (ipos >= 0) */
+#define OTM_PT_ANCHOR 32u      /* ... and not behind an earlier placed point of the step */
+#define OTM_PT_SAME_EDGE 64u   /* inside a same-edge step (forward along one edge, or a stay) */
+typedef struct otm_matched_point { /* 40 bytes */
+  int32_t edge;     /* directed edge id of the graph file; -1: no place */
+  uint32_t flags;   /* OTM_PT_* */
+  double lat, lon;  /* degrees, 0 when unmatched */
+  float offset;     /* metres from the edge's start */
+  float distance;   /* metres, input point to (lat, lon) */
+  int64_t way_id;   /* 0 when unmatched */
+} otm_matched_point;
+/* otm_set_points: the switch (on != 0).  otm_points_info: its value.
+ * otm_fetch_points answers for the handle's last otm_match_soa,
+ * otm_match_compact or otm_match_device batch, any number of times with the
+ * same bytes: *n_points records into dst[cap]; cap 0 with dst NULL only sizes
+ * the call.  On a multi-device engine the members' records are joined in the
+ * batch's point order.  otm_points_device: the device buffer of a one-device
+ * engine (valid until its next batch), ordered behind the engine's stream.
+ * OTM_EINVAL (message in otm_last_error): a NULL engine, a fetch with the
+ * switch off or before any batch ran with it on, cap below the point count,
+ * otm_points_device on a multi-device handle. */
+int otm_set_points(otm_engine* eng, int on);
+int otm_points_info(const otm_engine* eng, int* on);
+int otm_fetch_points(otm_engine* eng, otm_matched_point* dst, int64_t cap, int64_t* n_points);
+int otm_points_device(otm_engine* eng, const void** dev, int64_t* n_points);
+
 /* Per-segment speed histogram, accumulated on the device by every match
  * call: counts u32[n_segments * nbins], bin = floor(kph / bin_kph) clamped to
  * nbins-1, one count per datastore report.  The buffer is CALLER-owned device

@@ -131,6 +131,18 @@ TRACE_DTYPE = np.dtype([(n, "<i4") for n in (
     "unreported_count", "discontinuities", "invalid_speeds", "unassociated", "successful_length",
     "unreported_length")])
 
+# otm_matched_point (include/otmatch.h): 40 bytes, natural alignment
+POINT_DTYPE = np.dtype([("edge", "<i4"), ("flags", "<u4"), ("lat", "<f8"), ("lon", "<f8"), ("offset", "<f4"),
+                        ("distance", "<f4"), ("way_id", "<i8")])
+
+
+class MatchedPoint(C.Structure):
+    _fields_ = [("edge", C.c_int32), ("flags", C.c_uint32), ("lat", C.c_double), ("lon", C.c_double),
+                ("offset", C.c_float), ("distance", C.c_float), ("way_id", C.c_int64)]
+
+
+PT_MATCHED, PT_COLUMN, PT_NODE, PT_CHAIN_START, PT_ROUTE, PT_ANCHOR, PT_SAME_EDGE = 1, 2, 4, 8, 16, 32, 64
+
 SEG_START_VALID, SEG_END_VALID, SEG_INTERNAL, SEG_START_INT, SEG_END_INT = 1, 2, 4, 8, 16
 REP_T1_INT, REP_T0_INT = 1, 2
 REP_T1_INT_MINUS1 = REP_T1_INT
@@ -148,6 +160,10 @@ def _declare(L):
         "otm_config_meili": (C.c_int, [C.c_char_p, vp]),
         "otm_config_queue": (C.c_int, [C.c_char_p, C.POINTER(C.c_float)]),
         "otm_queue_info": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "otm_set_points": (C.c_int, [vp, C.c_int]),
+        "otm_points_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "otm_fetch_points": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
+        "otm_points_device": (C.c_int, [vp, pp, C.POINTER(i64)]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

@@ -2199,6 +2199,67 @@ int otm_queue_info(const otm_engine* E, float* kph) {
   return OTM_OK;
 }
 
+// Matched points (DESIGN.md §3 rule 7c): the per-handle switch and the last batch's records
+static_assert(sizeof(otm_matched_point) == 40 && alignof(otm_matched_point) == 8, "matched point record");
+
+int otm_set_points(otm_engine* E, int on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  std::lock_guard<std::mutex> lk(E->mu);
+  for (otm_engine* m : E->members) {
+    std::lock_guard<std::mutex> ml(m->mu);
+    m->points_on = on != 0;
+  }
+  E->points_on = on != 0;
+  return OTM_OK;
+}
+
+int otm_points_info(const otm_engine* E, int* on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (on) *on = E->points_on ? 1 : 0;
+  return OTM_OK;
+}
+
+static int otm_fetch_points_impl(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n_points) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "matched points: dst is NULL with cap != 0");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (!E->members.empty()) {
+    // the members' records of the group's last batch, joined in point order (group.cpp)
+    if (!E->points_on) return fail(OTM_EINVAL, "matched points are off (otm_set_points)");
+    if (E->g_pts_n < 0) return fail(OTM_EINVAL, "no batch has run with matched points on");
+    if (n_points) *n_points = E->g_pts_n;
+    if (!dst && cap == 0) return OTM_OK;
+    if (cap < E->g_pts_n) return fail(OTM_EINVAL, "matched points: cap below the batch's point count");
+    if (E->g_pts_n) std::memcpy(dst, E->g_pts.data(), (size_t)E->g_pts_n * sizeof(otm_matched_point));
+    return OTM_OK;
+  }
+  if (E->device >= 0) (void)hipSetDevice(E->device);
+  std::string err;
+  int rc = otm::engine_fetch_points(E, dst, cap, n_points, &err);
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n_points) {
+  try {
+    return otm_fetch_points_impl(E, dst, cap, n_points);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  } catch (const std::exception& e) {
+    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
+  }
+}
+
+int otm_points_device(otm_engine* E, const void** dev, int64_t* n_points) {
+  if (!E || !dev) return fail(OTM_EINVAL, "engine or dev is NULL");
+  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (!E->points_on) return fail(OTM_EINVAL, "matched points are off (otm_set_points)");
+  if (E->pts_n < 0) return fail(OTM_EINVAL, "no batch has run with matched points on");
+  *dev = E->pts_n ? E->pts.p : nullptr;
+  if (n_points) *n_points = E->pts_n;
+  return OTM_OK;
+}
+
 int otm_index_tables(const otm_engine* E, int64_t* slots, int64_t* bytes, int32_t* load_pct) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
   if (!E->members.empty()) E = E->members[0];

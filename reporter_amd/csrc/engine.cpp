@@ -436,6 +436,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->small_points = P->small_points;
   C->trans_lanes = P->trans_lanes;
   C->queue_kph = P->queue_kph;
+  C->points_on = P->points_on;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -656,7 +657,7 @@ void engine_free(otm_engine* E) {
       &E->o_segments,    &E->o_seg_gidx,   &E->o_way_ids,      &E->o_reports,  &E->o_rep_cnt,  &E->seg_ub,
       &E->f_seg_off,     &E->f_way_off,    &E->f_rep_off,      &E->f_segs,     &E->f_ways,     &E->f_reps,
       &E->f_traces,
-      &E->abort_flag,    &E->rs_blob,      &E->ord_tile,      &E->ord_cnt,      &E->ord_cursor,     &E->ord_grp,    &E->ord_item,
+      &E->abort_flag,    &E->pts,          &E->rs_blob,      &E->ord_tile,      &E->ord_cnt,      &E->ord_cursor,     &E->ord_grp,    &E->ord_item,
       &E->d_req,         &E->req_cnt,      &E->req_ok,     &E->req_lat,    &E->req_lon,    &E->req_time,   &E->req_acc,
       &E->resp_hdr,      &E->resp_seg,     &E->resp_rep,       &E->resp_hlen,      &E->resp_slen,  &E->resp_rlen,
       &E->resp_blen,     &E->resp_host,    &E->resp_blob,
@@ -674,7 +675,7 @@ void engine_free(otm_engine* E) {
     b->p = nullptr;
     b->cap = 0;
   }
-  for (auto* b : {&E->h_traces, &E->h_segs, &E->h_reps_dense, &E->h_ways, &E->h_tot, &E->h_in, &E->h_status,
+  for (auto* b : {&E->h_traces, &E->h_segs, &E->h_reps_dense, &E->h_ways, &E->h_tot, &E->h_in, &E->h_status, &E->h_pts,
                   &E->h_req, &E->h_req_ok, &E->h_resp, &E->h_resp_meta, &E->h_flush, &E->h_flush_meta}) {
     if (b->p) (void)hipHostFree(b->p);
     b->p = nullptr;
@@ -988,6 +989,14 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   launch_segments(E->g, b, w, o, true, s, mk);
   // K7b (DESIGN.md §3 rule 7b): only with a queue threshold; outside the timing marks
   if (E->queue_kph > 0.0f) launch_queue(b, w, o, E->queue_kph, s);
+  // K7c (DESIGN.md §3 rule 7c): only with the handle's switch on; outside the timing marks.
+  // Every attempt writes the whole array, so a redone or resumed batch leaves one run's records.
+  E->pts_n = -1;
+  if (E->points_on) {
+    ENS(pts, Pn * sizeof(otm_matched_point));
+    launch_points(E->g, b, dp, w, P<otm_matched_point>(E->pts), s);
+    E->pts_n = NP;
+  }
   launch_report(b, E->drc, w, o, s, mk);
   HIPCHK(hipGetLastError());
   E->last_T = NT;
@@ -1740,6 +1749,31 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
   }
   if (n) HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, E->stream));
   HIPCHK(hipStreamSynchronize(E->stream));
+  return OTM_OK;
+}
+
+int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err) {
+  if (!E->points_on) {
+    *err = "matched points are off (otm_set_points)";
+    return OTM_EINVAL;
+  }
+  if (E->pts_n < 0) {
+    *err = "no batch has run with matched points on";
+    return OTM_EINVAL;
+  }
+  if (n) *n = E->pts_n;
+  if (!dst && cap == 0) return OTM_OK;  // sizing call
+  if (!dst || cap < E->pts_n) {
+    *err = "matched points: cap below the batch's point count";
+    return OTM_EINVAL;
+  }
+  const size_t bytes = (size_t)E->pts_n * sizeof(otm_matched_point);
+  if (!bytes) return OTM_OK;
+  int rc;
+  if ((rc = ensure_pinned(E->h_pts, bytes, err))) return rc;
+  HIPCHK(big_copy(E->h_pts.p, E->pts.p, bytes, hipMemcpyDeviceToHost, E->stream));
+  HIPCHK(wait_batch(E, E->stream, E->pts_n));
+  std::memcpy(dst, E->h_pts.p, bytes);
   return OTM_OK;
 }
 

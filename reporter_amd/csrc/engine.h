@@ -237,6 +237,14 @@ struct otm_engine {
   std::mutex split_mu;
   otm::H2DOrder split_order;
   std::atomic<int> last_split{1};  // the chunks of the last otm_report_batch (otm_debug_last_split)
+  // matched points (otm_set_points, DESIGN.md §3 rule 7c; last, so every other member lies where it
+  // lay): off, a batch launches and allocates nothing for them.  pts: otm_matched_point[last_P] of the
+  // last batch that ran with the switch on (pts_n its count, -1: none); h_pts: the pinned staging of
+  // otm_fetch_points; g_pts: a multi-device engine's joined records (g_pts_n as pts_n)
+  bool points_on = false;
+  int64_t pts_n = -1, g_pts_n = -1;
+  Buf pts, h_pts;
+  std::vector<otm_matched_point> g_pts;
 };
 
 namespace otm {
@@ -296,6 +304,9 @@ int engine_copy_responses(otm_engine* E, char* dst, int64_t total, const char** 
 // copy results of the last batch to host vectors and describe them
 int engine_fetch(otm_engine* E, otm_results* out, std::string* err);
 int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t* needed, std::string* err);
+// the last batch's matched points (E->pts_n of them) copied to dst; OTM_EINVAL
+// when the switch is off, no batch ran with it on, or cap is below the count
+int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err);
 int engine_counters(otm_engine* E, otm_work_counters* out);
 // report() on the GPU over caller-supplied typed segments (otm_report_segments_device):
 // per trace t its points' times [trace_off[t], trace_off[t+1]) and segments

@@ -111,6 +111,7 @@ struct MemberOut {
   std::vector<otm_segment> segs;
   std::vector<otm_report_rec> reps;
   std::vector<int64_t> ways;
+  std::vector<otm_matched_point> pts;  // (with the matched-points switch on)
   int rc = 0;
   std::string err;
 };
@@ -126,6 +127,7 @@ void run_member(otm_engine* M, MemberOut& o) {
   sb.accuracy = o.acc.data();
   std::lock_guard<std::mutex> lk(M->mu);
   (void)hipSetDevice(M->device);
+  if (M->group) M->points_on = M->group->points_on;  // a group's batch runs with the group handle's switch
   otm_results r;
   o.rc = engine_match_host(M, &sb, &o.err);
   if (!o.rc) o.rc = engine_fetch(M, &r, &o.err);
@@ -135,6 +137,11 @@ void run_member(otm_engine* M, MemberOut& o) {
   o.segs.assign(r.segments, r.segments + r.n_segments);
   o.reps.assign(r.reports, r.reports + r.n_reports);
   o.ways.assign(r.way_ids, r.way_ids + r.n_way_ids);
+  if (M->points_on) {
+    int64_t n = 0;
+    o.pts.resize((size_t)sb.n_points);
+    o.rc = engine_fetch_points(M, o.pts.data(), sb.n_points, &n, &o.err);
+  }
 }
 
 int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_results* out, std::string* err) {
@@ -222,6 +229,17 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
     }
     G->g_reps.insert(G->g_reps.end(), o.reps.begin() + r0, o.reps.begin() + r0 + tr.rep_cnt);
     G->g_traces[(size_t)t] = tr;
+  }
+  // the members' matched points, joined in the batch's point order
+  G->g_pts_n = -1;
+  if (G->points_on) {
+    G->g_pts.resize((size_t)np);
+    for (int32_t t = 0; t < nt; ++t) {
+      const MemberOut& o = mo[(size_t)mem[(size_t)t]];
+      const int64_t m0 = o.off[(size_t)pos[(size_t)t]], m1 = o.off[(size_t)pos[(size_t)t] + 1];
+      std::copy(o.pts.begin() + m0, o.pts.begin() + m1, G->g_pts.begin() + (b->trace_off[t] - p0));
+    }
+    G->g_pts_n = np;
   }
   out->n_traces = nt;
   out->n_segments = (int32_t)G->g_segs.size();

@@ -382,6 +382,11 @@ void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o
 // K7b: queue_length of the complete OSMLR segments launch_segments wrote, at the
 // threshold kph > 0 (DESIGN.md §3 rule 7b); no timing slot of its own
 void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s);
+// K7c: one otm_matched_point per input point into out[n_points] (DESIGN.md §3
+// rule 7c), after launch_seg_bound placed the interpolated points; launched
+// only with the handle's switch on; no timing slot of its own
+void launch_points(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, otm_matched_point* out,
+                   hipStream_t s);
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);

@@ -4858,6 +4858,201 @@ __global__ __launch_bounds__(1024) void k_fetch_scan(int32_t n, const int32_t* c
   }
 }
 
+// ============================================================== K7c matched points
+// (after the pipeline's other kernels in this file, so that the code object lays those out as it did without it)
+// interp_pos's sibling (DESIGN.md §3 rule 7c): the same loop, tie rules and
+// f32 expressions, returning the winning piece's edge and the admissible
+// foot's offset on it instead of the route position (edge -1: none), so K7a's
+// path gets no store and the place is the one ipos names: xs + (off - o0).
+__device__ int2 interp_foot(const DevGraph& g, const DevBatch& b, const DevParams& P, const DevWork& w, int64_t q,
+                            int64_t p, int64_t k) {
+  const int2 ci = w.chosen[q], cj = w.chosen[p];
+  const int32_t ei = ci.x, ej = cj.x;
+  const float oi = __int_as_float(ci.y), oj = __int_as_float(cj.y);
+  const int32_t poff = w.path_off[p], plen = w.path_len[p];
+  const bool has0 = !cand_node(oi);
+  const int npc = (has0 ? 1 : 0) + plen + (cand_node(oj) ? 0 : 1);
+  const float start = src_start(g, ei, oi);
+  const float ds = (2.0f * P.sigma_z) * P.sigma_z;
+  const float lat = b.lat[k], lon = b.lon[k];
+  const float ls = MPD_F * cos_deg(lat);
+  const float gcd = gc_dist(b.lat[q], b.lon[q], lat, lon);
+  float best = INFINITY, dd = 0.0f, bo = 0.0f;
+  int32_t be = -1;
+  for (int m = 0; m < npc; ++m) {
+    RoutePiece pc;
+    const int pk = m - (has0 ? 1 : 0);
+    if (has0 && m == 0) {
+      pc = RoutePiece{ei, oi, g.e_len[ei], 0.0f};
+    } else if (pk < plen) {
+      const int32_t e = w.path_pool[poff + pk];
+      const float len = g.e_len[e];
+      pc = RoutePiece{e, 0.0f, len, start + dd};
+      dd = dd + len;
+    } else {
+      pc = RoutePiece{ej, 0.0f, oj, start + dd};
+    }
+    const int32_t s0 = g.e_shape_off[pc.edge], nsh = g.e_shape_off[pc.edge + 1] - s0 - 1;
+    float bsq = INFINITY, boff = 0.0f;
+    for (int sg = 0; sg < nsh; ++sg) {
+      float sqd, off;
+      project(g, pc.edge, sg, lat, lon, ls, sqd, off);
+      if (sqd < bsq) {
+        bsq = sqd;
+        boff = off;
+      }
+    }
+    if (!(boff >= pc.o0 && boff <= pc.o1)) continue;
+    const float pos = pc.xs + (boff - pc.o0);
+    const float cost = bsq / ds + fabsf(pos - gcd) / P.beta;
+    if (cost < best) {
+      best = cost;
+      be = pc.edge;
+      bo = boff;
+    }
+  }
+  return make_int2(be, __float_as_int(bo));
+}
+
+// The closest foot of point k on the whole of edge e (rule 7c, same-edge
+// steps): every shape segment, ties to the lowest, clamped into [lo, hi].
+__device__ float edge_foot(const DevGraph& g, const DevBatch& b, int32_t e, int64_t k, float lo, float hi) {
+  const float lat = b.lat[k], lon = b.lon[k];
+  const float ls = MPD_F * cos_deg(lat);
+  const int32_t nsh = g.e_shape_off[e + 1] - g.e_shape_off[e] - 1;
+  float bsq = INFINITY, boff = 0.0f;
+  for (int sg = 0; sg < nsh; ++sg) {
+    float sqd, off;
+    project(g, e, sg, lat, lon, ls, sqd, off);
+    if (sqd < bsq) {
+      bsq = sqd;
+      boff = off;
+    }
+  }
+  return boff < lo ? lo : (boff > hi ? hi : boff);
+}
+
+// One wavefront per trace, lanes over its points in chunks of 64 (k_queue's
+// shape); one 40-byte record per point, in input point order whatever the
+// launch plan.  A column with a state copies its chosen candidate; an
+// interpolated point finds its step from prevc / nextc as K7a does and, placed
+// (ipos >= 0), recomputes the winning piece's foot, or, in a same-edge step,
+// takes its clamped foot on the edge.  OTM_PT_ANCHOR needs the running maximum
+// of ipos over the step's earlier points: a segmented inclusive max-scan over
+// the wave (segments begin at columns, unplaced points count as -1), the
+// maximum carried from chunk to chunk for a step's run that crosses one -- no
+// lane walks its step.  Then per lane: the edge record, the walk over the
+// edge's cumulative lengths to the offset's shape segment, the coordinate and
+// the distance in double, and the record's store.  Every read of a per-point
+// array is of the trace's own points [a, a + n).
+__global__ __launch_bounds__(TB) void k_points(DevGraph g, DevBatch b, DevParams P, DevWork w,
+                                               otm_matched_point* out) {
+  if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
+  const int lane = threadIdx.x;
+  for (int32_t t = blockIdx.x; t < b.n_traces; t += gridDim.x) {
+    const int64_t a = b.trace_off[t];
+    const int n = (int)(b.trace_off[t + 1] - a);
+    const bool ok = w.trace_err[t] == 0;
+    float carry = -1.0f;  // the open step's maximum at the end of the previous chunk
+    for (int c0 = 0; c0 < n; c0 += TB) {
+      const int pl = c0 + lane;
+      const bool in = pl < n;
+      const int64_t k = a + pl;
+      bool col = false;
+      uint32_t flags = 0;
+      int32_t edge = -1;
+      float off = 0.0f, x = -1.0f;
+      if (in) {
+        col = w.is_col[k] != 0;
+        if (col) {
+          flags = OTM_PT_COLUMN;
+          if (ok && w.state[k] >= 0) {
+            const int2 c = w.chosen[k];
+            edge = c.x;
+            off = __int_as_float(c.y);
+            flags |= OTM_PT_MATCHED | (cand_node(off) ? OTM_PT_NODE : 0u) | (w.chain_start[k] ? OTM_PT_CHAIN_START : 0u);
+          }
+        } else if (ok) {
+          // the step q -> p around this point: linked, matched (k_seg_bound's test)
+          const int32_t q = w.prevc[k];
+          const int32_t p = q >= 0 ? w.nextc[q] : -1;
+          if (p >= 0 && w.col_prev[p] == q && !w.chain_start[p] && w.state[p] >= 0 && w.path_len[p] >= 0) {
+            const int2 ci = w.chosen[q], cj = w.chosen[p];
+            const float oi = __int_as_float(ci.y), oj = __int_as_float(cj.y);
+            if (same_edge_step(ci.x, oi, cj.x, oj)) {
+              edge = ci.x;
+              off = edge_foot(g, b, edge, k, oi < oj ? oi : oj, oi < oj ? oj : oi);
+              flags = OTM_PT_MATCHED | OTM_PT_SAME_EDGE;
+            } else {
+              x = w.ipos[k];
+              if (x >= 0.0f) {
+                const int2 f = interp_foot(g, b, P, w, q, p, k);
+                edge = f.x;
+                off = __int_as_float(f.y);
+                flags = OTM_PT_MATCHED | OTM_PT_ROUTE;
+              } else {
+                x = -1.0f;
+              }
+            }
+          }
+        }
+      }
+      // segmented inclusive max-scan of x: a column (or a lane past the trace) starts a segment
+      float v = x;
+      bool head = col || !in;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const float vn = __shfl_up(v, d, 64);
+        const int hn = __shfl_up((int)head, d, 64);
+        if (lane >= d) {
+          if (!head) v = vn > v ? vn : v;
+          head = head || hn != 0;
+        }
+      }
+      if (!head) v = carry > v ? carry : v;
+      carry = __shfl(v, 63, 64);
+      if ((flags & OTM_PT_ROUTE) && x >= v) flags |= OTM_PT_ANCHOR;
+      if (!in) continue;
+      otm_matched_point r;
+      r.edge = -1;
+      r.flags = flags;
+      r.lat = 0.0;
+      r.lon = 0.0;
+      r.offset = 0.0f;
+      r.distance = 0.0f;
+      r.way_id = 0;
+      const bool placed = (flags & OTM_PT_MATCHED) && edge >= 0;
+      const int32_t s0 = placed ? g.e_shape_off[edge] : 0;
+      const int32_t nsh = placed ? g.e_shape_off[edge + 1] - s0 - 1 : 0;
+      if (nsh >= 1) {  // (every edge of a graph file has a shape segment)
+        const uint4 er = g.e_rec[edge];
+        // the lowest shape segment with off <= cum[s + 1] (the last one when rounding left none)
+        int sg = 0;
+        float c1 = g.s_cum[s0 + 1];
+        while (sg + 1 < nsh && !(off <= c1)) {
+          ++sg;
+          c1 = g.s_cum[s0 + sg + 1];
+        }
+        const double c0d = (double)g.s_cum[s0 + sg], c1d = (double)c1;
+        const double tt = c1d == c0d ? 0.0 : ((double)off - c0d) / (c1d - c0d);
+        const double la0 = (double)g.s_lat[s0 + sg], lo0 = (double)g.s_lon[s0 + sg];
+        r.lat = la0 + tt * ((double)g.s_lat[s0 + sg + 1] - la0);
+        r.lon = lo0 + tt * ((double)g.s_lon[s0 + sg + 1] - lo0);
+        const double plat = (double)b.lat[k], plon = (double)b.lon[k];
+        const double ls = 111319.4954833 * cos(plat * 0.017453292519943295);
+        const double dx = (r.lon - plon) * ls, dy = (r.lat - plat) * 111319.4954833;
+        r.distance = (float)sqrt(dx * dx + dy * dy);
+        r.edge = edge;
+        r.offset = off;
+        r.way_id = g.way_tab[er.w];
+      } else {
+        r.flags = flags & OTM_PT_COLUMN;  // no place: a column keeps its flag alone
+      }
+      out[k] = r;
+    }
+  }
+}
+
 int grid_for(int64_t n, int per_block, int cap) {
   int64_t g = (n + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -5123,6 +5318,10 @@ void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o
 }
 void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s) {
   hipLaunchKernelGGL(k_queue, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w, o, kph);
+}
+void launch_points(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, otm_matched_point* out,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(k_points, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g, b, p, w, out);
 }
 void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* tb, hipStream_t s,
                       const Marks& mk) {

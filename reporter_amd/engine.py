@@ -124,10 +124,13 @@ class Results(object):
 
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
-                 trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, **meili):
+                 trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, matched_points=False,
+                 **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
-        with ndev > 1): traces go to member murmur2(uuid) % ndev."""
+        with ndev > 1): traces go to member murmur2(uuid) % ndev.
+        matched_points: the per-point records of DESIGN.md §3 rule 7c
+        (set_points / points; off: nothing changes)."""
         L = lib()
         self._tmp = None
         if config_path is None:
@@ -147,6 +150,8 @@ class Engine(object):
         self.h = h
         self.device = devs[0]
         self.devices = devs
+        if matched_points:
+            self.set_points(True)
 
     def members(self):
         """Member count: ndev of a multi-device engine, else 1."""
@@ -429,6 +434,33 @@ class Engine(object):
         k = C.c_float()
         _check(lib().otm_queue_info(self.h, C.byref(k)))
         return k.value
+
+    def set_points(self, on):
+        """The matched-points switch of this handle (otm_set_points; a multi-device
+        engine passes it to every member, a clone inherits it when it is made)."""
+        _check(lib().otm_set_points(self.h, 1 if on else 0))
+
+    def points_info(self):
+        """Whether matched points are on (otm_points_info)."""
+        on = C.c_int()
+        _check(lib().otm_points_info(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def points(self):
+        """The last binary-level batch's matched points (otm_fetch_points): one
+        _lib.POINT_DTYPE record per input point, in input order."""
+        n = C.c_int64()
+        _check(lib().otm_fetch_points(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=_lib.POINT_DTYPE)
+        _check(lib().otm_fetch_points(self.h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def points_device(self):
+        """(device pointer, count) of the last batch's records in this GPU's HBM
+        (otm_points_device; a one-device engine's, valid until its next batch)."""
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().otm_points_device(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))
