@@ -918,7 +918,15 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     scan_i64(w.trans_off, NP, E->scan_tmp.p, E->scan_tmp.cap, s);
     mk.end(KN_SCAN_TRANS, s);
   }
-  ENS(trans, ((size_t)E->trans_cap + 1) * 4);
+  {
+    // k_viterbi_row prefetches whole windows: past a chunk's blocks it reads
+    // whatever the allocation holds there (never past trans_cap), and that
+    // must never be a NaN.  So a new allocation starts as zeros; from then on
+    // it holds only costs, this batch's or an earlier one's.
+    const size_t cap0 = E->trans.cap;
+    ENS(trans, ((size_t)E->trans_cap + 1) * 4);
+    if (E->trans.cap != cap0) HIPCHK(hipMemsetAsync(E->trans.p, 0, E->trans.cap, s));
+  }
   w.trans = P<float>(E->trans);
   w.trans_cap = E->trans_cap;
   if (!fold_bookkeeping()) launch_cap_check(b, w, s);

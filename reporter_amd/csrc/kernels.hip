@@ -3123,7 +3123,7 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
 
 // K5, one DPP row per trace (16 lanes, lane j = state j: four traces per
 // wavefront) -- the form for batches between the wave form's
-// and the grouped forms' (launch_viterbi: 8,192 to 32,767 traces).  The
+// and the grouped forms' (launch_viterbi: 4,096 to 32,767 traces).  The
 // previous column's scores never leave their registers: a DPP
 // row_newbcast hands lane i of each 16-lane row to the whole row as an operand
 // of the add, so prev[i] + T[i][j] is one VALU instruction and the serial
@@ -3136,14 +3136,20 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
 //    the current chunk is stepped; the blocks are staged through a per-row LDS
 //    window at the chunk's start, the emissions stay in their lane; a chunk
 //    whose blocks exceed the window copies each step's block at the step;
+//  * a step in which every row is idle, at an interpolated point or at a
+//    column linked to its open chain inside the window (98.8 % of config 2's)
+//    takes a fast path chosen wave-uniformly: the recurrence, the nibbles and
+//    the chain's last column, nothing else (OTM_VR_FAST=0: never);
 //  * backpointers as nibbles in LDS, a chain's end records its argmin, one
 //    lane per row walks backward at the end; outputs point-parallel.
 // DPP reads of a lane that EXEC has switched off do not return its value, so
 // the recurrence runs with every lane enabled and masks by selects: `prev` is
 // +inf in the lanes past a column's count (a source past Kq never wins), and
 // what a lane reads from the windows for such a source, for a target past Kp
-// or for an unlinked row is a transition float or +inf (the windows start as
-// +inf and are only ever staged from this batch's blocks), never a NaN.
+// or for an unlinked row is a cost (>= +0, +inf included) or a zero, never a
+// NaN: the windows start as +inf and are only ever staged from the transition
+// allocation, which starts as zeros and only ever holds costs (ld_data below;
+// no read leaves the allocation).
 // A trace with more than VR_PTS points or a column of more than 16 candidates
 // goes to `rej`, for the wave form in list mode.  Same recurrence (min over i
 // in order, strict <, the fours' min tree and first-index select), tie rules
@@ -3158,6 +3164,10 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
 #define OTM_VR_WAVES 3
 #endif
 constexpr int VR_PTS = 128;  // points per trace
+// four floats of the transition stream, which is aligned to a float only (a
+// global_load_dwordx4 needs no more)
+typedef float vr_f4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef float vr_f4a __attribute__((ext_vector_type(4)));  // (in LDS: 16-byte aligned)
 // four sources i = I0 .. I0 + 3 of the recurrence: their window reads (issued
 // for all of a step's fours before the first is used), then the sums (the DPP
 // control is an immediate) and the running minimum
@@ -3168,43 +3178,56 @@ __device__ __forceinline__ void vr_load(const float* Tm, const int Kp, float (&t
 }
 template <int I0>
 __device__ __forceinline__ void vr_four(const int pbits, const float (&tv)[16], float& best, int& bi) {
-  const float v0 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 0, 0xF, 0xF, false)) + tv[I0 + 0];
-  const float v1 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 1, 0xF, 0xF, false)) + tv[I0 + 1];
-  const float v2 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 2, 0xF, 0xF, false)) + tv[I0 + 2];
-  const float v3 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 3, 0xF, 0xF, false)) + tv[I0 + 3];
+  float v0 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 0, 0xF, 0xF, false)) + tv[I0 + 0];
+  float v1 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 1, 0xF, 0xF, false)) + tv[I0 + 1];
+  float v2 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 2, 0xF, 0xF, false)) + tv[I0 + 2];
+  float v3 = __int_as_float(__builtin_amdgcn_update_dpp(0, pbits, 0x150 + I0 + 3, 0xF, 0xF, false)) + tv[I0 + 3];
+  // Each sum's bits through an empty asm: the SLP vectoriser otherwise packs
+  // half of the sums into a v_mov_b32_dpp per source and a v_pk_add_f32 per
+  // pair, which costs more issue than the two v_add_f32_dpp it replaces.
+  // From there on the bits are compared as integers: the costs are >= +0
+  // (no NaN, no -0; +inf included), where the signed order of the bits is the
+  // floats' order, and an integer min needs no canonicalising v_max of a
+  // value the compiler cannot see into.
+  int i0 = __float_as_int(v0), i1 = __float_as_int(v1), i2 = __float_as_int(v2), i3 = __float_as_int(v3);
+  asm("" : "+v"(i0));
+  asm("" : "+v"(i1));
+  asm("" : "+v"(i2));
+  asm("" : "+v"(i3));
   // in i order with strict <: the four's minimum, if below best, at the
-  // first u that reaches it (k_viterbi's form; costs >= +0: no NaN or -0);
-  // selects, not branches
-  const float m = fminf(fminf(v0, v1), fminf(v2, v3));
+  // first u that reaches it (k_viterbi's form); selects, not branches
+  const int m = min(min(i0, i1), min(i2, i3));
   int fu = 3;
-  fu = v2 == m ? 2 : fu;
-  fu = v1 == m ? 1 : fu;
-  fu = v0 == m ? 0 : fu;
-  const bool lt = m < best;
-  best = lt ? m : best;
+  fu = i2 == m ? 2 : fu;
+  fu = i1 == m ? 1 : fu;
+  fu = i0 == m ? 0 : fu;
+  const bool lt = m < __float_as_int(best);
+  best = lt ? __int_as_float(m) : best;
   bi = lt ? I0 + fu : bi;
 }
 // win: the window's floats a chunk may use (<= VT; the tests force the
 // per-step path with a small one)
 __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, DevWork w, int32_t* rej, int32_t* rej_n,
-                                                                  int win, int snap) {
+                                                                  int win, int fast, int snap) {
   constexpr int G = 16, NT = TB / G;
   constexpr int CH = OTM_VR_CH, U = OTM_VR_U;
   constexpr int VT = U * G;                    // transition floats per chunk window
   constexpr int VTA = VT > G * G ? VT : G * G;  // (a window holds any one column pair's block)
   constexpr int RS = VTA + G;                  // row stride: row g starts g x 16 banks on
-  static_assert(CH >= 1 && CH <= G && U >= 1, "chunk knobs");
+  static_assert(CH >= 1 && CH <= G && U >= 4 && U % 4 == 0, "chunk knobs");
+  static_assert(RS % 4 == 0, "a row's window is staged by 16-byte stores");
   // spill snapshot B (see k_viterbi)
   if (OTM_FOLD_BOOKKEEPING && snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, 1, true);
   if (*w.abort) return;
   // the rows' windows, then G x G floats that stay +inf: a masked source's
   // read (up to 255 floats past a block's start) stays inside
-  __shared__ float sT[NT * RS + G * G];
+  __shared__ __attribute__((aligned(16))) float sT[NT * RS + G * G];
   // a nibble per state (15: dead): [point * 8 + state / 2]
   __shared__ __attribute__((aligned(8))) uint8_t sBp[NT][VR_PTS * G / 2];
   // flags; after the walk: VG_CS | (state + 1) << 3
   __shared__ __attribute__((aligned(8))) uint8_t sFl[NT][VR_PTS];
-  __shared__ uint32_t sM[NT][VR_PTS + G];      // K3's byte | (trans_off[p] - trans_off[a]) << 8; [n]: the trace's end
+  // K3's byte | (trans_off[p] - trans_off[a]) << 8; [n]: the trace's end (a chunk's four words: one 16-byte read)
+  __shared__ __attribute__((aligned(16))) uint32_t sM[NT][VR_PTS + G];
   const int lane = threadIdx.x;
   const int g = lane / G, j = lane % G, gb = g * G;
   for (int f = lane; f < NT * RS + G * G; f += TB) sT[f] = INFINITY;
@@ -3256,31 +3279,58 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
     if (!act) n = 0;
     // (wave-uniform, and said so: the chunk loop is a scalar one)
     const int nch = __builtin_amdgcn_readfirstlane((wave_max_i(n) + CH - 1) / CH);
-    for (int pl = j; pl < ((n + 3) & ~3); pl += G) sFl[g][pl] = 0;  // (the walk reads four points' flags a turn)
+    // VG_COL for a column with candidates, from the words this lane wrote
+    // above (a plain step leaves its flag byte alone); the walk reads four
+    // points' flags a turn
+    for (int pl = j; pl < ((n + 3) & ~3); pl += G) {
+      const uint32_t m = sM[g][pl];
+      sFl[g][pl] = (uint8_t)(pl < n && (m & 0x40u) && (m & 0x3Fu) ? VG_COL : 0);
+    }
     wave_sync();
     const int nl = n > 0 ? n - 1 : 0;
-    // chunk c's float range in the trace's stream (an idle row: empty)
-    auto rng = [&](int c, int& lo, int& hi) {
-      const int p0 = c * CH < n ? c * CH : n, p1 = c * CH + CH < n ? c * CH + CH : n;
-      lo = act ? (int)(sM[g][p0] >> 8) : 0;
-      hi = act ? (int)(sM[g][p1] >> 8) : 0;
+    // where chunk c's floats end in the trace's stream, which is where chunk
+    // c + 1's begin (an idle row: empty, at the stream's start)
+    auto rng_end = [&](int c) {
+      const int p1 = c * CH + CH < n ? c * CH + CH : n;
+      return act ? (int)(sM[g][p1] >> 8) : 0;
     };
-    // raw values, indices clamped (past hi: the chunk's first float again)
-    float pT[U], pE[CH];
+    // this lane's emissions: one pointer and stride for the trace
+    const float* const ep = j < KIN ? w.cand_em + a * KIN + j : w.cand_xem + a * KX + (j - KIN);
+    const int es = j < KIN ? KIN : KX;
+    // A chunk's window: the VT floats from its first on, four to a lane and
+    // load (window float f = q * 4 G + 4 j + e is the stream's lo + f), by one
+    // pointer with immediate offsets.  Where every row's VT floats lie inside
+    // the allocation (trans_cap floats) nothing is clamped: what lies past a
+    // chunk's end is the stream's next floats or what the allocation holds
+    // behind the batch's last block, which is costs of this or an earlier
+    // batch or the zeros it was created with (engine.cpp), never a NaN.
+    // Within VT floats of the allocation's end, element by element with the
+    // index clamped into the chunk (past hi: the chunk's first float again).
+    vr_f4 pT[U / 4];
+    float pE[CH];
     auto ld_data = [&](int c, int lo, int hi) {
+      const int64_t f0 = t0 + lo;
+      if (__ballot(f0 + VT > w.trans_cap) == 0ull) {
+        const float* const tp = w.trans + (f0 + 4 * j);
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int f = lo + u * G + j;
-        pT[u] = w.trans[t0 + (f < hi ? f : lo)];
+        for (int q = 0; q < U / 4; ++q) pT[q] = *(const vr_f4*)(tp + q * 4 * G);
+      } else {
+#pragma unroll
+        for (int q = 0; q < U / 4; ++q) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int f = lo + q * 4 * G + 4 * j + e;
+            pT[q][e] = w.trans[t0 + (f < hi ? f : lo)];
+          }
+        }
       }
 #pragma unroll
       for (int k = 0; k < CH; ++k) {
         const int pl = c * CH + k < nl ? c * CH + k : nl;
-        pE[k] = j < KIN ? w.cand_em[(a + pl) * KIN + j] : w.cand_xem[(a + pl) * KX + (j - KIN)];
+        pE[k] = ep[pl * es];
       }
     };
-    int lo_n, hi_n;
-    rng(0, lo_n, hi_n);
+    int lo_n = 0, hi_n = rng_end(0);
     ld_data(0, lo_n, hi_n);
     // ---- forward pass (wave-uniform step count; rows masked by selects)
     float prev = INFINITY;
@@ -3302,22 +3352,24 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
       if (j == 0) sFl[g][last] = (uint8_t)(sFl[g][last] | VG_END | (bi << 3));
     };
     for (int c = 0; c < nch; ++c) {
-      // stage chunk c's blocks (a row without any: +inf, not whatever the
-      // clamped loads found), keep its emissions, read its points' words;
-      // then chunk c + 1's loads, in flight behind the steps
+      // stage chunk c's window (every load was inside the allocation and
+      // found a cost or a zero: see ld_data), keep its emissions, read its
+      // points' words (past the trace's end the row's LDS words, inside sM,
+      // are whatever they were, and `on` is false there); then chunk c + 1's
+      // loads, in flight behind the steps
       const int lo_c = lo_n, hi_c = hi_n;
-      const bool any = hi_c > lo_c;
 #pragma unroll
-      for (int u = 0; u < U; ++u) sTg[u * G + j] = any ? pT[u] : INFINITY;
+      for (int q = 0; q < U / 4; ++q) *(vr_f4a*)(sTg + q * 4 * G + 4 * j) = pT[q];
       float em_c[CH];
       uint32_t mw[CH];
 #pragma unroll
       for (int k = 0; k < CH; ++k) {
         em_c[k] = pE[k];
-        mw[k] = sM[g][c * CH + k < nl ? c * CH + k : nl];
+        mw[k] = sM[g][c * CH + k];
       }
       wave_sync();
-      rng(c + 1, lo_n, hi_n);
+      lo_n = hi_c;
+      hi_n = rng_end(c + 1);
       ld_data(c + 1, lo_n, hi_n);
       const bool big = hi_c - lo_c > win;  // this row's chunk overflowed its window
 #pragma unroll
@@ -3329,10 +3381,59 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
         const bool col = on && Kp > 0;
         // (a linked column's previous column is the open chain's last)
         const bool link = col && open && (mk & 0x80);
+        const float em = em_c[k];
+        // ---- the plain step: every row of the wave is idle, at an
+        // interpolated point (both: !on, nothing changes), or at a column
+        // that links to its open chain with its block in the window.  Only
+        // the recurrence, the nibbles and the chain's last column: no chain
+        // end, no chain start, no flag byte (VG_COL stands since set-up).
+        // A linked row in which no state is alive leaves it: that step, like
+        // every one that is not plain, runs the general body below, which
+        // has seen none of this one's work.
+        // (a bool's ballot as the compiler's own, a scalar and of the
+        // condition's mask: __ballot's goes through a select and a compare)
+        if (fast && __builtin_amdgcn_ballot_w64(on && (!link || big)) == 0ull) {
+          const unsigned long long lb = __builtin_amdgcn_ballot_w64(link);
+          bool done = true;
+          if (lb != 0ull) {
+            float best = INFINITY;
+            int bi = -1;
+            const int pbits = __float_as_int(prev);
+            const float* Tm = sTg + (link ? (int)(mw[k] >> 8) - lo_c : 0) + j;
+            const int KpL = link ? Kp : 0;
+            const int Kq = link ? lastK : 0;
+            const bool g1 = __ballot(Kq > 4) != 0ull, g2 = __ballot(Kq > 8) != 0ull, g3 = __ballot(Kq > 12) != 0ull;
+            float tv[16];
+            vr_load<0>(Tm, KpL, tv);
+            if (g1) vr_load<4>(Tm, KpL, tv);
+            if (g2) vr_load<8>(Tm, KpL, tv);
+            if (g3) vr_load<12>(Tm, KpL, tv);
+            vr_four<0>(pbits, tv, best, bi);
+            if (g1) vr_four<4>(pbits, tv, best, bi);
+            if (g2) vr_four<8>(pbits, tv, best, bi);
+            if (g3) vr_four<12>(pbits, tv, best, bi);
+            const bool alive = link && j < Kp && bi >= 0;
+            // bit 16 r + 15: a state of row r is alive (scalar work: a row's
+            // 16 bits are not zero when adding 0x7FFF to the low 15 carries
+            // into the 16th, or the 16th is set)
+            const unsigned long long ab = __builtin_amdgcn_ballot_w64(alive);
+            const unsigned long long any = ((ab & 0x7FFF7FFF7FFF7FFFull) + 0x7FFF7FFF7FFF7FFFull) | ab;
+            done = (lb & ~any & 0x8000800080008000ull) == 0ull;
+            if (done) {
+              const int nib = alive ? bi : 15;
+              const int pair = __builtin_amdgcn_mov_dpp(nib, 0xB1, 0xF, 0xF, false);
+              if (link && !(j & 1)) sBp[g][pl * (G / 2) + (j >> 1)] = (uint8_t)(nib | (pair << 4));
+              const float cur = alive ? best + em : INFINITY;
+              prev = link ? cur : prev;
+              last = link ? pl : last;
+              lastK = link ? Kp : lastK;
+            }
+          }
+          if (done) continue;
+        }
         // the open chain ends before a column without candidates and before
         // one that does not link to it
         if (on && open && !link) end_chain();
-        const float em = em_c[k];
         int tb = link ? (int)(mw[k] >> 8) - lo_c : 0;
         if (__ballot(big && link) != 0ull) {
           // the column's block (<= G x G floats) into the window first, so
@@ -5219,7 +5320,7 @@ void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p
 }
 void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk) {
   // the form: OTM_VIT_FORM (4: the row form, 8, 16 or 64) for the tests; by
-  // default the grouped forms from 32,768 traces up, the row form from 8,192
+  // default the grouped forms from 32,768 traces up, the row form from 4,096
   // and the wave form below.  Why the grouped forms start that high:
   // a small batch's waves all fit the GPU at once, so its time is one wave's
   // (~100 steps of a latency-bound chain either way), while a large batch's
@@ -5230,11 +5331,12 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   const char* fe = std::getenv("OTM_VIT_FORM");
   const int forced = fe ? std::atoi(fe) : 0;
   constexpr int gmin = 32768;
-  // the row form from 8,192 traces: below, a batch's waves are few enough per
+  // the row form from 4,096 traces: below, a batch's waves are few enough per
   // SIMD that a step's latency, not VALU issue, sets its time, and the wave
-  // form's step is the shorter one (profiles/viterbi_row/sweep.json: 61 us
-  // against 81 + 5 at 512 traces, even at 6,144, 125 against 103 + 5 at 8,192)
-  constexpr int rmin = 8192;
+  // form's step is the shorter one (profiles/viterbi_plain/sweep.json: 61 us
+  // against 65 + 5 at 512 traces, 69 against 69 + 5 at 2,048, 84 against
+  // 76 + 5 at 4,096, 123 against 84 + 5 at 8,192)
+  constexpr int rmin = 4096;
   const int form = forced ? forced : (b.n_traces >= gmin ? 8 : (b.n_traces >= rmin ? 4 : 64));
   if (form == 4) {
     // the row form (k_viterbi_row: four traces per wave) over every trace;
@@ -5246,9 +5348,12 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
     const int vt = OTM_VR_U * 16;
     int win = we ? std::atoi(we) : vt;
     win = win < 0 ? 0 : (win > vt ? vt : win);
+    // OTM_VR_FAST=0: every step through the general body (A/B runs, tests)
+    const char* fa = std::getenv("OTM_VR_FAST");
+    const int fast = fa ? (std::atoi(fa) != 0 ? 1 : 0) : 1;
     mk.begin(KN_VITERBI, s);
     hipLaunchKernelGGL(k_viterbi_row, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
-                       w.overflow_list2, w.counters_i32 + 26, win, 1);
+                       w.overflow_list2, w.counters_i32 + 26, win, fast, 1);
     // (sized for every trace, as a batch of long traces needs: a block whose
     // list entries ran out exits at once)
     hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
