@@ -649,11 +649,11 @@ void engine_free(otm_engine* E) {
       &E->cand_xeo,      &E->cand_xem,
       &E->probe,         &E->col_prev,     &E->kq_prev,        &E->vmeta,  &E->colrec, &E->colrec_pos,        &E->trans_off,      &E->trans,          &E->bp,         &E->state,      &E->chosen,
       &E->chain_start,   &E->route_dist,   &E->ipos,   &E->path_off,       &E->path_len,       &E->path_pool,  &E->trace_err,
-      &E->overflow_list0, &E->overflow_list2, &E->counters_i32, &E->scan_tmp, &E->snap,   &E->big_key,
+      &E->spill_list1, &E->spill_list2, &E->counters_i32, &E->scan_tmp, &E->snap,   &E->big_key,
       &E->big_lab,       &E->big_inq,      &E->big_fr,         &E->big_ins,        &E->big_prev,
       &E->huge_key,      &E->huge_lab,     &E->huge_inq,       &E->huge_fr,        &E->huge_ins,         &E->huge_prev,
       &E->cbig_key,      &E->cbig_val,     &E->cbig_skey,
-      &E->overflow_list3, &E->o_traces,       &E->o_seg_cnt,  &E->o_way_cnt,
+      &E->spill_list3, &E->o_traces,       &E->o_seg_cnt,  &E->o_way_cnt,
       &E->o_segments,    &E->o_seg_gidx,   &E->o_way_ids,      &E->o_reports,  &E->o_rep_cnt,  &E->seg_ub,
       &E->f_seg_off,     &E->f_way_off,    &E->f_rep_off,      &E->f_segs,     &E->f_ways,     &E->f_reps,
       &E->f_traces,
@@ -800,11 +800,11 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   ENS(path_off, Pn * 4);
   ENS(path_len, Pn * 4);
   ENS(trace_err, ((size_t)NT + 1) * 4);
-  ENS(overflow_list0, Pn * 4);
-  ENS(overflow_list2, Pn * 4);
-  ENS(overflow_list3, Pn * 4);
-  ENS(counters_i32, 64 * 4);  // 64 counters (kernels.h DevWork::counters_i32)
-  ENS(snap, 192 + sizeof(BatchStatus));
+  ENS(spill_list1, Pn * 4);
+  ENS(spill_list2, Pn * 4);
+  ENS(spill_list3, Pn * 4);
+  ENS(counters_i32, CTR_WORDS * 4);  // (kernels.h CtrSlot)
+  ENS(snap, sizeof(SnapBuf));
   ENS(abort_flag, 16);
   // Capacities of the transition matrices and the path pool: sized from the
   // batch (kept at the largest seen), so the abort -> regrow -> redo loop of
@@ -867,19 +867,18 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   w.path_pool = P<int32_t>(E->path_pool);
   w.pool_cap = E->pool_cap;
   w.trace_err = P<int32_t>(E->trace_err);
-  w.overflow_list0 = P<int32_t>(E->overflow_list0);
-  w.overflow_list2 = P<int32_t>(E->overflow_list2);
-  w.overflow_list3 = P<int32_t>(E->overflow_list3);
+  w.spill_list1 = P<int32_t>(E->spill_list1);
+  w.spill_list2 = P<int32_t>(E->spill_list2);
+  w.spill_list3 = P<int32_t>(E->spill_list3);
   w.idx = E->idx;
   for (int l = 0; l < NEAR_LEVELS; ++l) w.idxn[l] = E->idxn[l];
   w.counters_i32 = P<int32_t>(E->counters_i32);
-  w.snap = P<int32_t>(E->snap);
+  w.snap = &P<SnapBuf>(E->snap)->stage[0][0];
   w.ctr = E->counting ? E->ctr : nullptr;
   if (E->counting && from == RESUME_ALL) HIPCHK(hipMemsetAsync(E->ctr, 0, sizeof(DevCounters), s));
   w.abort = P<int32_t>(E->abort_flag);
   // the counters' and abort flag's reset, the spill snapshots and the
-  // transition capacity check ride in K1, K3, K4, K5 and K7 (OTM_FOLD_BOOKKEEPING)
-  if (!fold_bookkeeping()) launch_batch_init(w.counters_i32, w.abort, s);  // [5] = candidate spill count
+  // transition capacity check ride in K1, K3, K4, K5 and K7 (kernels.h CtrSlot)
   Marks mk;
   mk.ev = E->timing ? E->kev : nullptr;
   ENS(ord_tile, Pn * 2);
@@ -908,10 +907,8 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   w.cbig_skey = P<unsigned long long>(E->cbig_skey);
   w.cand_log2 = E->cand_log2;
   if (from <= RESUME_CAND_BIG) launch_candidates(E->g, b, dp, w, s, mk, from);
-  // spill snapshot A: candidate probes the lane tier handed to the wave tier;
-  // the counters start over for the transition tiers (links, scan and the
-  // capacity check do not touch them)
-  if (!fold_bookkeeping()) launch_snap(w.counters_i32, P<int32_t>(E->snap), true, s);
+  // (k_links takes SNAP_AFTER_CAND: candidate probes the lane tier handed to
+  // the wave tier; the counters start over for the transition tiers)
   if (from <= RESUME_CAND_BIG) {
     launch_links(b, dp, w, s, mk);
     mk.begin(KN_SCAN_TRANS, s);
@@ -929,7 +926,6 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   }
   w.trans = P<float>(E->trans);
   w.trans_cap = E->trans_cap;
-  if (!fold_bookkeeping()) launch_cap_check(b, w, s);
   if ((rc = ensure_big(E, err))) return rc;
   w.big_key = P<uint32_t>(E->big_key);
   w.big_lab = P<unsigned long long>(E->big_lab);
@@ -947,13 +943,11 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   w.huge_log2 = E->huge_log2;
   w.huge_final = E->huge_final;
   if (from <= RESUME_TRANS_HUGE) launch_transitions(E->g, b, dp, w, s, mk, E->trans_lanes, from);
-  // spill snapshot B: columns per transition tier (Viterbi does not touch
-  // the counters; they start over for the route tiers)
-  if (!fold_bookkeeping()) launch_snap(w.counters_i32, P<int32_t>(E->snap) + 16, true, s);
+  // (the first Viterbi launch takes SNAP_AFTER_TRANS: columns per transition
+  // tier; the per-stage counters start over for the route tiers)
   if (from <= RESUME_TRANS_HUGE) launch_viterbi(b, w, s, mk);
   launch_route(E->g, b, dp, w, s, mk, from);
-  // spill snapshot C: steps per route tier
-  if (!fold_bookkeeping()) launch_snap(w.counters_i32, P<int32_t>(E->snap) + 32, false, s);
+  // (k_seg_bound takes SNAP_AFTER_ROUTE: steps per route tier)
 
   // Segments, way ids and reports in ONE walk per trace, each trace writing
   // into a region sized by an upper bound (DevOut): every matched point adds
@@ -994,7 +988,7 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   mk.begin(KN_SEG_SCAN, s);
   scan_i64(P<int64_t>(E->seg_ub), NT, E->scan_tmp.p, E->scan_tmp.cap, s);
   mk.end(KN_SEG_SCAN, s);
-  launch_segments(E->g, b, w, o, true, s, mk);
+  launch_segments(E->g, b, w, o, s, mk);
   // K7b (DESIGN.md §3 rule 7b): only with a queue threshold; outside the timing marks
   if (E->queue_kph > 0.0f) launch_queue(b, w, o, E->queue_kph, s);
   // K7c (DESIGN.md §3 rule 7c): only with the handle's switch on; outside the timing marks.
@@ -1037,14 +1031,13 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     // the one synchronisation of a batch: did every capacity hold?
     // (gathered on the device, one copy into pinned memory)
     if ((rc = ensure_pinned(E->h_status, sizeof(BatchStatus), err))) return rc;
-    BatchStatus* dst = (BatchStatus*)(P<char>(E->snap) + 192);
+    BatchStatus* dst = &P<SnapBuf>(E->snap)->status;
     launch_status(P<int32_t>(E->abort_flag), P<int64_t>(E->trans_off) + NP, P<int32_t>(E->counters_i32), dst, s);
     HIPCHK(hipMemcpyAsync(E->h_status.p, dst, sizeof(BatchStatus), hipMemcpyDeviceToHost, s));
     HIPCHK(wait_batch(E, s, NP));
     const BatchStatus st = *(const BatchStatus*)E->h_status.p;
     const int32_t ab = st.abort;
     const int64_t ttotal = st.ttotal;
-    const int32_t cnt[3] = {st.cnt[0], st.cnt[1], st.cnt[2]};
     E->last_trans = ttotal;
     E->last_attempts = attempt + 1;
     if (!ab) break;
@@ -1053,7 +1046,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       return OTM_EDEVICE;
     }
     if (ttotal > E->trans_cap) E->trans_cap = ttotal + ttotal / 4 + 4096;
-    if (st.grow & 1) {
+    if (st.grow & GROW_HUGE) {
       // a search outgrew the huge tier's tables (or found none): 4x the slots,
       // or, past the cap or out of HBM, the overflowing traces fail alone
       const int32_t next = E->huge_log2 ? E->huge_log2 + 2 : 19;
@@ -1071,7 +1064,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
         }
       }
     }
-    if (st.grow & 2) {
+    if (st.grow & GROW_CAND) {
       // a probe had more distinct edges in its radius than the candidate
       // HBM tier's tables hold (or there were none): 4x the slots, or the
       // overflowing traces fail alone
@@ -1089,7 +1082,8 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
         }
       }
     }
-    if (cnt[2]) E->pool_cap = (int32_t)std::min<size_t>((size_t)cnt[1] * 2 + 1024, (size_t)INT32_MAX / 2);
+    if (st.pool_over)
+      E->pool_cap = (int32_t)std::min<size_t>((size_t)st.pool_used * 2 + 1024, (size_t)INT32_MAX / 2);
     // Where to resume: a matrix or path-pool overflow redoes
     // the whole batch (those buffers are reallocated); a tier whose tables
     // grew -- candidate HBM tier, or the huge search tier of the transition
@@ -1099,16 +1093,18 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     // that stage's boundary (A after the candidates, B after the transitions,
     // C after the routes), so the resumed kernels retake the same snapshots.
     const char* nr = std::getenv("OTM_NO_RESUME");  // A/B knob: every redo whole (rounds 1-5)
-    const bool whole = !fold_bookkeeping() || ttotal > E->trans_cap || cnt[2] || !(st.grow & 3) ||
+    const bool whole = ttotal > E->trans_cap || st.pool_over || !(st.grow & (GROW_HUGE | GROW_CAND)) ||
                        (nr && *nr && *nr != '0');
     from = whole ? RESUME_ALL
-                 : (st.grow & 2) ? RESUME_CAND_BIG : (st.route_huge ? RESUME_ROUTE_HUGE : RESUME_TRANS_HUGE);
+                 : (st.grow & GROW_CAND) ? RESUME_CAND_BIG : (st.route_huge ? RESUME_ROUTE_HUGE : RESUME_TRANS_HUGE);
     if (from != RESUME_ALL) {
-      const int snap = from == RESUME_CAND_BIG ? 0 : (from == RESUME_TRANS_HUGE ? 16 : 32);
+      const SnapId snap = from == RESUME_CAND_BIG ? SNAP_AFTER_CAND
+                                                  : (from == RESUME_TRANS_HUGE ? SNAP_AFTER_TRANS : SNAP_AFTER_ROUTE);
       int32_t* ctr = P<int32_t>(E->counters_i32);
-      HIPCHK(hipMemcpyAsync(ctr, P<int32_t>(E->snap) + snap, 16 * 4, hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemsetAsync(ctr + 23, 0, 4, s));  // the grow flags
-      HIPCHK(hipMemsetAsync(ctr + 25, 0, 4, s));
+      HIPCHK(hipMemcpyAsync(ctr, P<SnapBuf>(E->snap)->stage[snap], CTR_STAGE_WORDS * sizeof(int32_t),
+                            hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemsetAsync(ctr + CTR_GROW_HUGE, 0, 4, s));
+      HIPCHK(hipMemsetAsync(ctr + CTR_GROW_CAND, 0, 4, s));
       HIPCHK(hipMemsetAsync(E->abort_flag.p, 0, 4, s));
       E->last_resumes += 1;
     }
@@ -1786,22 +1782,21 @@ int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int6
 }
 
 int engine_spill_stats(otm_engine* E, otm_spill_stats* out) {
-  int32_t v[48] = {};
+  // the per-stage counts from the stage boundaries' snapshots, the per-batch ones as they stand
+  int32_t v[SNAP_COUNT][CTR_STAGE_WORDS] = {};
   if (E->snap.p && hipMemcpy(v, E->snap.p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return OTM_EDEVICE;
-  // counters_i32 layout: [5] candidate spills; [4] index misses, [0] lane
-  // spills, [3] LDS-wave spills (per stage)
-  out->cand_wave = v[5];
-  out->trans_online = v[16 + 4];
-  out->trans_wave = v[16 + 4];
-  out->trans_global = v[16 + 3];
-  out->route_online = v[32 + 4];
-  out->route_wave = v[32 + 4];
-  out->route_global = v[32 + 3];
-  int32_t c[32] = {};
+  out->cand_wave = v[SNAP_AFTER_CAND][CTR_CAND_WAVE];
+  out->trans_online = v[SNAP_AFTER_TRANS][CTR_INDEX_MISS];
+  out->trans_wave = v[SNAP_AFTER_TRANS][CTR_INDEX_MISS];
+  out->trans_global = v[SNAP_AFTER_TRANS][CTR_SEARCH_GLOBAL];
+  out->route_online = v[SNAP_AFTER_ROUTE][CTR_INDEX_MISS];
+  out->route_wave = v[SNAP_AFTER_ROUTE][CTR_INDEX_MISS];
+  out->route_global = v[SNAP_AFTER_ROUTE][CTR_SEARCH_GLOBAL];
+  int32_t c[CTR_ZEROED_WORDS] = {};
   if (E->snap.p && hipMemcpy(c, E->counters_i32.p, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return OTM_EDEVICE;
-  out->cand_big = c[24];
-  out->trans_huge = c[21];
-  out->route_huge = c[22];
+  out->cand_big = c[CTR_CAND_BIG];
+  out->trans_huge = c[CTR_TRANS_HUGE];
+  out->route_huge = c[CTR_ROUTE_HUGE];
   out->attempts = E->last_attempts;
   out->resumed = E->last_resumes;
   return OTM_OK;

@@ -105,10 +105,10 @@ struct otm_engine {
   Buf in_off, in_lat, in_lon, in_time, in_acc, in_blob;
   // work
   Buf pt_trace, is_col, prevc, nextc, gc, ncand, cand_eo, cand_em, cand_xeo, cand_xem, probe, col_prev, kq_prev, vmeta, colrec, colrec_pos, trans_off, trans, bp, state, chosen,
-      chain_start, route_dist, ipos, path_off, path_len, path_pool, trace_err, overflow_list0, overflow_list2,
+      chain_start, route_dist, ipos, path_off, path_len, path_pool, trace_err, spill_list1, spill_list2,
       counters_i32, scan_tmp, snap;
   Buf big_key, big_lab, big_inq, big_fr, big_ins, big_prev;
-  Buf huge_key, huge_lab, huge_inq, huge_fr, huge_ins, huge_prev, overflow_list3;
+  Buf huge_key, huge_lab, huge_inq, huge_fr, huge_ins, huge_prev, spill_list3;
   int32_t huge_log2 = 0;  // huge search tier: 2^huge_log2 slots per table (0: none yet; grown on demand)
   int32_t huge_ready_log2 = 0;  // the layout the huge tables were last cleared for
   Buf cbig_key, cbig_val, cbig_skey;

@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "otmatch.h"
@@ -133,9 +134,6 @@ struct IdxRow {
 // 64 a record never straddles a 128-B line, but the records take a third more
 // lines of cache: config 4's k_trans_sub 1.340 ms at 64 against 1.328 at 48
 // (1.389 without the records; config 2 the same at both).
-#ifndef OTM_SRC_REC
-#define OTM_SRC_REC 1  // 0: the sources read DevGraph::e_fl, then DevIndex::row (A/B)
-#endif
 #ifndef OTM_SRC_REC_BYTES
 #define OTM_SRC_REC_BYTES 48
 #endif
@@ -219,6 +217,93 @@ struct DevCounters {
   unsigned long long segments_out, reports_out;
 };
 
+// ---- The batch protocol's words: DevWork::counters_i32 and the spill lists.
+//
+// A stage's kernels hand the work a tier cannot take to the next tier through
+// a list of point (or trace) numbers in one of DevWork::spill_list1..3 and its
+// entry count in a slot of counters_i32; the filler appends with an atomicAdd
+// on the count (spill_push), the drainer reads both on the device (spill_of),
+// so no tier costs a host round trip.  The lists are reused from stage to
+// stage; ctr_list() below says which list a count belongs to.
+//
+// Slots below CTR_STAGE_WORDS are per stage: block 0 of k_columns (K1) zeroes
+// them, fold_snap copies them to snapshot k of SnapBuf and resets them at the
+// stage boundaries SNAP_AFTER_CAND (in k_links) and SNAP_AFTER_TRANS (in the
+// first Viterbi launch), and copies them without a reset at SNAP_AFTER_ROUTE
+// (in k_seg_bound); engine_match copies a snapshot back into them when a batch
+// resumes at a tier whose tables grew, and engine_spill_stats reads the
+// snapshots.  Slots from CTR_STAGE_WORDS to CTR_ZEROED_WORDS are per batch:
+// K1 alone zeroes them, so they survive the stage boundaries and a resume
+// (which is what the resumed tier's list count needs); the host clears the two
+// grow flags before a resume.
+//
+//   slot               list  filled by -> drained by
+//   CTR_UNUSED         -     free (nothing writes or reads it)
+//   CTR_POOL_USED      -     path-pool words taken (k_route_index, k_route); read by k_status
+//   CTR_POOL_OVER      -     flag: the pool overflowed (the host grows pool_cap, redoes the batch)
+//   CTR_SEARCH_GLOBAL  2     LDS search tier -> global tier, in the transition stage
+//                            (k_transitions<0> -> <1>) and again in the route stage (k_route<0> -> <1>)
+//   CTR_INDEX_MISS     1     what the route index cannot answer -> LDS search tier: k_trans_sub ->
+//                            k_transitions<0>, then k_route_index -> k_route<0>
+//   CTR_CAND_WAVE      1     candidate lane tier -> wave tier (k_cand_lane -> k_candidates<false>)
+//   CTR_TRANS_WIDE     2     k_trans_sub<8, false>'s wide columns -> k_trans_sub<16, true>
+//   CTR_SEG_LARGE      1     k_segments' small plan -> its large plan (launch_segments), after
+//                            SNAP_AFTER_ROUTE: in no snapshot, zero whenever a snapshot is copied back
+//   CTR_VIT_16         1     Viterbi 8 lanes per trace -> 16 lanes (launch_viterbi)
+//   CTR_TRANS_HUGE     3     global tier -> huge tier, transitions (k_transitions<1> -> <2>)
+//   CTR_ROUTE_HUGE     3     global tier -> huge tier, routes (k_route<1> -> <2>); non-zero also tells
+//                            the host which stage's huge tier to resume at (BatchStatus::route_huge)
+//   CTR_GROW_HUGE      -     flag: the huge tier needs (larger) tables (huge_unready, huge_overflow)
+//   CTR_CAND_BIG       3     candidate wave tier -> HBM tier (k_candidates<false> -> <true>)
+//   CTR_GROW_CAND      -     flag: the candidate HBM tier needs (larger) tables (k_candidates)
+//   CTR_VIT_WAVE       2     Viterbi row form or 16 lanes -> wave form (launch_viterbi)
+//
+// The Viterbi counts are per batch, not per stage: SNAP_AFTER_TRANS is taken
+// (and the per-stage slots reset) by one thread of the first Viterbi launch,
+// whose other blocks are appending to these lists by then.  Lists 1 and 2 are
+// free between the transition and route stages, and an attempt that aborted
+// earlier skips Viterbi, so the counts are filled once per batch.
+enum CtrSlot : int {
+  CTR_UNUSED = 0,
+  CTR_POOL_USED = 1,
+  CTR_POOL_OVER = 2,
+  CTR_SEARCH_GLOBAL = 3,
+  CTR_INDEX_MISS = 4,
+  CTR_CAND_WAVE = 5,
+  CTR_TRANS_WIDE = 6,
+  CTR_SEG_LARGE = 8,
+  CTR_VIT_16 = 20,
+  CTR_TRANS_HUGE = 21,
+  CTR_ROUTE_HUGE = 22,
+  CTR_GROW_HUGE = 23,
+  CTR_CAND_BIG = 24,
+  CTR_GROW_CAND = 25,
+  CTR_VIT_WAVE = 26,
+};
+constexpr int CTR_STAGE_WORDS = 16;   // per stage: snapshot and reset
+constexpr int CTR_ZEROED_WORDS = 32;  // per stage + per batch: zeroed by K1
+constexpr int CTR_WORDS = 64;         // allocated
+enum SnapId : int { SNAP_AFTER_CAND = 0, SNAP_AFTER_TRANS = 1, SNAP_AFTER_ROUTE = 2, SNAP_COUNT = 3 };
+// which of DevWork::spill_list1..3 the count in slot c belongs to (0: c counts no list)
+constexpr int ctr_list(CtrSlot c) {
+  switch (c) {
+    case CTR_INDEX_MISS: case CTR_CAND_WAVE: case CTR_SEG_LARGE: case CTR_VIT_16: return 1;
+    case CTR_SEARCH_GLOBAL: case CTR_TRANS_WIDE: case CTR_VIT_WAVE: return 2;
+    case CTR_TRANS_HUGE: case CTR_ROUTE_HUGE: case CTR_CAND_BIG: return 3;
+    default: return 0;
+  }
+}
+constexpr bool ctr_per_stage(CtrSlot c) { return c >= 0 && c < CTR_STAGE_WORDS; }
+constexpr bool ctr_per_batch(CtrSlot c) { return c >= CTR_STAGE_WORDS && c < CTR_ZEROED_WORDS; }
+static_assert(ctr_per_stage(CTR_UNUSED) && ctr_per_stage(CTR_POOL_USED) && ctr_per_stage(CTR_POOL_OVER) &&
+                  ctr_per_stage(CTR_SEARCH_GLOBAL) && ctr_per_stage(CTR_INDEX_MISS) && ctr_per_stage(CTR_CAND_WAVE) &&
+                  ctr_per_stage(CTR_TRANS_WIDE) && ctr_per_stage(CTR_SEG_LARGE),
+              "per-stage slots lie in the snapshot range");
+static_assert(ctr_per_batch(CTR_VIT_16) && ctr_per_batch(CTR_TRANS_HUGE) && ctr_per_batch(CTR_ROUTE_HUGE) &&
+                  ctr_per_batch(CTR_GROW_HUGE) && ctr_per_batch(CTR_CAND_BIG) && ctr_per_batch(CTR_GROW_CAND) &&
+                  ctr_per_batch(CTR_VIT_WAVE),
+              "per-batch slots lie past the snapshot range, within what K1 zeroes");
+
 // per-point / per-trace work arrays of one batch (device pointers)
 struct DevWork {
   int32_t* pt_trace;     // [P] trace of point
@@ -253,14 +338,10 @@ struct DevWork {
   int32_t* path_pool;    // [pool_cap]
   int32_t pool_cap;
   int32_t* trace_err;    // [T]
-  int32_t* overflow_list0; // [P] columns/steps the index could not answer
-  int32_t* overflow_list2; // [P] ... the LDS search tier spilled (and k_trans_sub's wide columns)
-  int32_t* snap;           // [48] spill snapshots A (after K2), B (after K4), C (after K6)
-  int32_t* counters_i32;   // [64]: [1] pool used, [2] pool overflow flag, [3] list 2 count, [4] list 0 count,
-                           // [5] candidate wave-tier count, [6] wide list count (0-15: per stage, snapshot
-                           // and reset); per batch: [20] Viterbi wide list, [21] / [22] huge-tier
-                           // transition / route searches, [23] huge grow flag, [24] candidate HBM-tier
-                           // probes, [25] its grow flag
+  int32_t* spill_list1;    // [P] a stage's first spill list (CtrSlot above: who fills and drains it when)
+  int32_t* spill_list2;    // [P] ... its second
+  int32_t* snap;           // SnapBuf::stage: the per-stage counters at the three stage boundaries
+  int32_t* counters_i32;   // [CTR_WORDS] indexed by CtrSlot
   int32_t* abort;          // [1] set when a capacity (transition matrices, path pool) was exceeded:
                            // every later kernel returns at once and the host redoes the batch
   int64_t trans_cap;       // floats allocated for w.trans
@@ -295,9 +376,24 @@ struct DevWork {
   unsigned long long* cbig_skey;  // [CAND_BIG_SLOTS << (cand_log2 - 1)]
   int32_t cand_log2;
   int32_t cand_final;      // the candidate tables cannot grow: an overflowing probe fails its trace (500)
-  int32_t* overflow_list3; // [P] searches the global tier spilled (counts: [21] transitions, [22] route)
+  int32_t* spill_list3;    // [P] the list of a tier whose tables the host sizes (huge search, candidate HBM)
   DevCounters* ctr;        // nullptr when counting is off
 };
+// a spill list with its entry count, by the count's slot
+struct SpillRef {
+  int32_t* list;
+  int32_t* count;
+};
+template <CtrSlot C>
+__host__ __device__ __forceinline__ int32_t* spill_list(const DevWork& w) {
+  constexpr int L = ctr_list(C);
+  static_assert(L != 0, "this slot counts no list");
+  return L == 1 ? w.spill_list1 : (L == 2 ? w.spill_list2 : w.spill_list3);
+}
+template <CtrSlot C>
+__host__ __device__ __forceinline__ SpillRef spill_of(const DevWork& w) {
+  return SpillRef{spill_list<C>(w), w.counters_i32 + C};
+}
 
 // Outputs of one batch.  Segments, way ids and reports are written in one
 // pass into per-trace regions sized by an upper bound (2 traversals per
@@ -368,17 +464,15 @@ enum Resume { RESUME_ALL = 0, RESUME_CAND_BIG = 1, RESUME_TRANS_HUGE = 2, RESUME
 void launch_candidates(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
                        const Marks& mk, int from = RESUME_ALL);
 void launch_links(const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s, const Marks& mk);
-// sets *w.abort when the scanned transition total exceeds w.trans_cap
-void launch_cap_check(const DevBatch& b, DevWork& w, hipStream_t s);
 // index tier -> LDS search tier -> global tier, spill lists on the device
-// (counters_i32[3] / [4] / [6] must be zero on entry)
+// (CTR_SEARCH_GLOBAL, CTR_INDEX_MISS and CTR_TRANS_WIDE must be zero on entry);
+// the first kernel sets *w.abort when the scanned transition total exceeds w.trans_cap
 void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
                         const Marks& mk, int sub, int from = RESUME_ALL);
 void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);
 void launch_route(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
                   const Marks& mk, int from = RESUME_ALL);
-void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, bool write, hipStream_t s,
-                     const Marks& mk);
+void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // K7b: queue_length of the complete OSMLR segments launch_segments wrote, at the
 // threshold kph > 0 (DESIGN.md §3 rule 7b); no timing slot of its own
 void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s);
@@ -408,19 +502,22 @@ void launch_index_build(const DevGraph& g, const uint32_t* turn_units, uint32_t 
 int index_load_fast();
 int index_load_dense();
 void launch_row_sizes(const int32_t* row_cnt, int64_t* row_sizes, int32_t n, int pct, hipStream_t s);
+constexpr int32_t GROW_HUGE = 1, GROW_CAND = 2;  // BatchStatus::grow bits (CTR_GROW_HUGE, CTR_GROW_CAND set)
 struct BatchStatus {
-  int32_t abort, grow;  // grow bit 0: the huge search tier needs (larger) tables; bit 1: the candidate HBM tier
+  int32_t abort, grow;
   int64_t ttotal;
-  int32_t cnt[3];
-  int32_t route_huge;   // counters_i32[22]: the route stage reached its huge tier (else the transition stage did)
+  int32_t pool_used, pool_over;  // CTR_POOL_USED, CTR_POOL_OVER
+  int32_t route_huge;   // CTR_ROUTE_HUGE: the route stage reached its huge tier (else the transition stage did)
 };
-void launch_batch_init(int32_t* counters, int32_t* abort, hipStream_t s);
+// otm_engine::snap: the spill snapshots (DevWork::snap), then k_status's staging area
+struct SnapBuf {
+  int32_t stage[SNAP_COUNT][CTR_STAGE_WORDS];
+  BatchStatus status;
+};
+static_assert(offsetof(SnapBuf, status) == 192 && sizeof(SnapBuf) == 192 + 32, "snapshot buffer layout");
 // otm_match_compact's inputs widened on the device (time = base + delta, accuracy as float)
 void launch_expand_compact(const int64_t* trace_off, const int64_t* tbase, const int32_t* dt, const int16_t* acc16,
                            double* time, float* acc, int32_t n_traces, hipStream_t s);
-void launch_snap(int32_t* counters, int32_t* snap, bool reset, hipStream_t s);
-// batch bookkeeping folded into the stage kernels (no launches of their own)
-bool fold_bookkeeping();
 void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out,
                    hipStream_t s);
 void launch_row_pack(const int32_t* row_cnt, const int64_t* row_off, IdxRow* rows, int32_t n, hipStream_t s);

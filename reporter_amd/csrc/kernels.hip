@@ -251,22 +251,24 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 
-// The same bookkeeping folded into the stage kernels: each kernel boundary in
-// a stream costs ~5-10 us, and these ran as five one-wave launches per batch.
-#ifndef OTM_FOLD_BOOKKEEPING
-#define OTM_FOLD_BOOKKEEPING 1
-#endif
-// one thread: spill snapshot k (16 counters), optionally resetting them
+// The batch bookkeeping is folded into the stage kernels: each kernel boundary
+// in a stream costs ~5-10 us, and it once ran as five one-wave launches per batch.
+// one thread: spill snapshot k of the per-stage counters, optionally resetting them
 __device__ __forceinline__ void fold_snap(DevWork& w, int k, bool reset) {
-  for (int t = 0; t < 16; ++t) {
-    w.snap[16 * k + t] = w.counters_i32[t];
+  for (int t = 0; t < CTR_STAGE_WORDS; ++t) {
+    w.snap[CTR_STAGE_WORDS * k + t] = w.counters_i32[t];
     if (reset) w.counters_i32[t] = 0;
   }
+}
+// one lane: p onto the list that slot C counts
+template <CtrSlot C>
+__device__ __forceinline__ void spill_push(const DevWork& w, int32_t p) {
+  const SpillRef s = spill_of<C>(w);
+  s.list[atomicAdd(s.count, 1)] = p;
 }
 // every transition kernel's first test: the matrices' total against the
 // buffer (the first kernel to run sets the abort flag for the rest)
 __device__ __forceinline__ bool trans_over_cap(const DevBatch& b, const DevWork& w) {
-  if (!OTM_FOLD_BOOKKEEPING) return false;
   if (w.trans_off[b.n_points] <= w.trans_cap) return false;
   *w.abort = 1;
   return true;
@@ -399,9 +401,9 @@ __global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParam
   __shared__ int32_t sPrev[COL_PTS];
   __shared__ uint8_t sCol[COL_PTS];
   const int lane = threadIdx.x;
-  if (OTM_FOLD_BOOKKEEPING && blockIdx.x == 0) {
-    // the batch's tier counters and abort flag start at zero (k_batch_init)
-    if (lane < 32) w.counters_i32[lane] = 0;  // ([20]: the wide Viterbi list)
+  if (blockIdx.x == 0) {
+    // the batch's tier counters (per stage and per batch) and abort flag start at zero
+    if (lane < CTR_ZEROED_WORDS) w.counters_i32[lane] = 0;
     if (lane == 0) *w.abort = 0;
   }
   for (int32_t t = blockIdx.x; t < b.n_traces; t += gridDim.x) {
@@ -559,21 +561,13 @@ constexpr int CAND_LANE_CAP = OTM_CAND_LANE_CAP;
 #define OTM_CAND_WAVES 8
 #endif
 constexpr int CAND_TB = OTM_CAND_TB;
-// lane tier: where a kept entry's offset along its edge (the snap pass's
-// projection) waits for the output loop, which then loads no graph word:
-//   2  in registers, one per list slot in snap order, found through a packed
-//      8 x 3-bit permutation word that the merge's move and the sort's swaps
-//      update (no LDS, the 64-VGPR cap and 8 waves per SIMD kept)
-//   1  in a third LDS array beside sE / sQ (96 B per thread: 6 waves per SIMD;
-//      build with OTM_CAND_WAVES=6)
-//   0  nowhere: the output loop projects each chosen edge entry again (the
-//      form up to round 6: nine more loads in two round trips per candidate)
-// k_cand_lane on config 2: 197.9 us at 0, 194.1 at 2, 211.2 at 1 (222.1 with
-// OTM_SNAP_B=4, 16 B of scratch at 80 VGPRs); config 4: 1342 at 0, 1274 at 2
-// (profiles/graph_words/)
-#ifndef OTM_CAND_OFF
-#define OTM_CAND_OFF 2
-#endif
+// lane tier: a kept entry's offset along its edge (the snap pass's
+// projection) waits for the output loop, which then loads no graph word, in
+// registers: one per list slot in snap order, found through a packed 8 x 3-bit
+// permutation word that the merge's move and the sort's swaps update (no LDS,
+// the 64-VGPR cap and 8 waves per SIMD kept).  Against projecting each chosen
+// entry again in the output loop, and against a third LDS array: DESIGN.md §5
+// K2, profiles/graph_words/
 #ifndef OTM_CAND_INFL
 #define OTM_CAND_INFL 2
 #endif
@@ -584,15 +578,6 @@ constexpr int CAND_INFL = OTM_CAND_INFL;
 #define OTM_SNAP_B 2
 #endif
 constexpr int SNAP_B = OTM_SNAP_B;
-// transition index tier: pairs per lane whose first slot loads are issued
-// together.  Round 2 measured 2 best (0.337 -> 0.302 ms on config 2, 1.956 ->
-// 1.888 ms on config 4; 3 and 4 slower: registers, spills); on round 4's
-// kernel 1 is (0.213 / 0.251 / 0.298 ms for 1 / 2 / 3 on config 2, 2.164 /
-// 2.351 / 2.478 ms on config 4, profiles/r04_ab/trans_batch/)
-#ifndef OTM_TRANS_BATCH
-#define OTM_TRANS_BATCH 1
-#endif
-
 // wave-reduce a per-lane count and add it to a device counter (all 64 lanes active)
 __device__ __forceinline__ void wave_cadd(unsigned long long* c, unsigned long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -612,12 +597,7 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
   __shared__ float sQ[CAND_LANE_CAP * CAND_TB];     // best squared distance
   uint32_t* E = sE + threadIdx.x;
   float* Q = sQ + threadIdx.x;
-#if OTM_CAND_OFF == 1
-  __shared__ float sO[CAND_LANE_CAP * CAND_TB];  // offset along the edge (snap pass)
-  float* O = sO + threadIdx.x;
-#elif OTM_CAND_OFF == 2
   static_assert(CAND_LANE_CAP <= 8 && CAND_LANE_CAP % SNAP_B == 0, "3-bit slots; whole snap steps");
-#endif
   constexpr int S = CAND_TB;
   unsigned long long c_cells = 0, c_ent = 0, c_cand = 0;
   const ItemRange R = item_range(w, b, (P.order_mask & ORDER_CAND) != 0, CAND_TB);
@@ -625,8 +605,7 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
     const int64_t p = R.ordered ? (int64_t)w.ord.item[it] : it;
     if (!R.ordered && !w.is_col[p]) continue;
     if (P.cand_wave_all) {
-      const int slot = atomicAdd(&w.counters_i32[5], 1);
-      w.overflow_list0[slot] = (int32_t)p;
+      spill_push<CTR_CAND_WAVE>(w, (int32_t)p);
       continue;
     }
     const float4 pr = w.probe[p];  // {lat, lon, accuracy} of the column (K1), one line
@@ -714,8 +693,7 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
       }
     }
     if (spill) {
-      const int slot = atomicAdd(&w.counters_i32[5], 1);
-      w.overflow_list0[slot] = (int32_t)p;
+      spill_push<CTR_CAND_WAVE>(w, (int32_t)p);
       continue;
     }
     // node snap: an entry whose projection snaps to a node becomes that
@@ -731,7 +709,6 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
     // s_lon that proj_load reads (engine_init copies them), and seg_sqdist is
     // proj_calc's sqd operation for operation (no contraction): where l2 > 0
     // the same t, elsewhere both take t = 0.
-#if OTM_CAND_OFF == 2
     float offr[CAND_LANE_CAP];  // by snap-pass slot; perm: list slot -> snap-pass slot
     uint32_t perm = 076543210u;
 #pragma unroll
@@ -740,9 +717,6 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
 #pragma unroll
       for (int u = 0; u < SNAP_B; ++u) offr[m0 + u] = 0.0f;
       if (m0 >= n) continue;
-#else
-    for (int m0 = 0; m0 < n; m0 += SNAP_B) {
-#endif
       uint32_t em[SNAP_B];
       ProjIn pin[SNAP_B];
 #pragma unroll
@@ -778,11 +752,7 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
             offv[u] = 0.0f;
           }
         }
-#if OTM_CAND_OFF == 1
-        if (m0 + u < n) O[(m0 + u) * S] = offv[u];
-#elif OTM_CAND_OFF == 2
         offr[m0 + u] = offv[u];
-#endif
       }
     }
     for (int m = 0; m < n; ++m) {
@@ -797,11 +767,7 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         --n;  // drop entry m: the last entry moves here and is examined next
         E[m * S] = E[n * S];
         Q[m * S] = Q[n * S];
-#if OTM_CAND_OFF == 1
-        O[m * S] = O[n * S];
-#elif OTM_CAND_OFF == 2
         perm = (perm & ~(7u << (3 * m))) | ((perm >> (3 * n)) & 7u) << (3 * m);
-#endif
         --m;
       }
     }
@@ -827,14 +793,8 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         E[m * S] = E[j * S];
         Q[j * S] = qm;
         E[j * S] = em;
-#if OTM_CAND_OFF == 1
-        const float om = O[m * S];
-        O[m * S] = O[j * S];
-        O[j * S] = om;
-#elif OTM_CAND_OFF == 2
         const uint32_t x = ((perm >> (3 * m)) ^ (perm >> (3 * j))) & 7u;  // swap slots m and j
         perm ^= x << (3 * m) | x << (3 * j);
-#endif
       }
     }
     // the K chosen, in order: the point's inline blocks whole (its 8-B
@@ -858,18 +818,11 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
         if (jj < K) {
           const uint32_t en = E[jj * S];
           const int32_t e = (int32_t)((en & ~NODE_ENT) >> 4);
-#if OTM_CAND_OFF == 0
-          float sqd = Q[jj * S], off = 0.0f;
-          if (!(en & NODE_ENT)) project(g, e, (int32_t)(en & 15u), lat, lon, ls, sqd, off);
-#elif OTM_CAND_OFF == 1
-          const float sqd = Q[jj * S], off = O[jj * S];
-#else
           const float sqd = Q[jj * S];
           const uint32_t sl = (perm >> (3 * jj)) & 7u;
           float off = offr[0];
 #pragma unroll
           for (int t = 1; t < CAND_LANE_CAP; ++t) off = sl == (uint32_t)t ? offr[t] : off;
-#endif
           e2[u] = e;
           o2[u] = off;
           emj = sqd / ds;
@@ -930,7 +883,7 @@ struct Mem<true> {  // global scratch: keep every access at L2 (agent scope)
 
 // Wave tier: one wavefront per spilled probe (list from the lane tier).
 // BIG = false: LDS tables (MAX_HITS distinct edges); a probe with more goes
-// to the list of the BIG form (overflow_list3, count [24]), whose tables
+// to the list of the BIG form (CTR_CAND_BIG), whose tables
 // (2^cand_log2 slots per block, in HBM) the host sizes: none until needed,
 // grown 4x with the batch redone when a probe does not fit (no limit on the
 // edges within a radius but memory; round 4 dropped the 256-edge spec limit).
@@ -943,8 +896,9 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
   __shared__ int cexcl[64];
   __shared__ int s_count, s_over, s_n;
   const int lane = threadIdx.x;
-  const int64_t nwork = BIG ? w.counters_i32[24] : w.counters_i32[5];
-  const int32_t* list = BIG ? w.overflow_list3 : w.overflow_list0;
+  const SpillRef work = BIG ? spill_of<CTR_CAND_BIG>(w) : spill_of<CTR_CAND_WAVE>(w);
+  const int64_t nwork = *work.count;
+  const int32_t* list = work.list;
   if (BIG && nwork > 0 && w.cand_log2 == 0) {
     // no tables yet: the host makes them and redoes the batch -- or, when it
     // cannot (cand_final), these probes' traces answer 500 (OTM_TERR_CAND_OVERFLOW)
@@ -953,7 +907,7 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
       if (w.cand_final) atomicCAS(&w.trace_err[w.pt_trace[list[it]]], 0, OTM_TERR_CAND_OVERFLOW);
     }
     if (!w.cand_final && blockIdx.x == 0 && lane == 0) {
-      w.counters_i32[25] = 1;
+      w.counters_i32[CTR_GROW_CAND] = 1;
       *w.abort = 1;
     }
     return;
@@ -1054,7 +1008,7 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
     if (s_over) {
       if (lane == 0) {
         if (!BIG) {
-          w.overflow_list3[atomicAdd(&w.counters_i32[24], 1)] = (int32_t)p;  // to the HBM tables
+          spill_push<CTR_CAND_BIG>(w, (int32_t)p);  // to the HBM tables
         } else if (w.cand_final) {
           // the tables are as large as they get: this probe's trace fails
           // alone (500, OTM_TERR_CAND_OVERFLOW), the batch goes on
@@ -1062,7 +1016,7 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
           atomicCAS(&w.trace_err[w.pt_trace[p]], 0, OTM_TERR_CAND_OVERFLOW);
         } else {
           w.ncand[p] = 0;
-          w.counters_i32[25] = 1;  // the tables are too small: grow, redo the batch
+          w.counters_i32[CTR_GROW_CAND] = 1;  // the tables are too small: grow, redo the batch
           *w.abort = 1;
         }
       }
@@ -1181,7 +1135,7 @@ __global__ __launch_bounds__(256) void k_links(DevBatch b, DevParams P, DevWork 
     w.trans_off[p] = 0;
     // spill snapshot A: candidate probes the lane tier handed to the wave
     // tier; the counters start over for the transition tiers
-    if (OTM_FOLD_BOOKKEEPING) fold_snap(w, 0, true);
+    fold_snap(w, SNAP_AFTER_CAND, true);
     return;
   }
   int32_t cp = -1, kq = 0;
@@ -1207,43 +1161,20 @@ __global__ __launch_bounds__(256) void k_links(DevBatch b, DevParams P, DevWork 
   w.vmeta[p] = (uint8_t)((w.is_col[p] ? (w.ncand[p] | 0x40) : 0) | (cp >= 0 ? 0x80 : 0));
 }
 
-// Batch bookkeeping in single-wave kernels rather than memset / memcpy
-// commands: each runtime copy or fill is its own blit dispatch (3.5-8 us
-// each on the stream, ~60 us per batch before).
-__global__ void k_batch_init(int32_t* counters, int32_t* abort) {
-  const int t = threadIdx.x;
-  if (t < 32) counters[t] = 0;
-  if (t == 0) *abort = 0;
-}
-// spill snapshot: copy the 16 tier counters, optionally zeroing them for the
-// next stage's tiers
-__global__ void k_snap(int32_t* counters, int32_t* snap, int reset) {
-  const int t = threadIdx.x;
-  if (t < 16) {
-    snap[t] = counters[t];
-    if (reset) counters[t] = 0;
-  }
-}
-// the batch's status for the host's one synchronisation: abort flag,
-// transition total, path-pool counters
+// The batch's status for the host's one synchronisation: abort flag,
+// transition total, path-pool counters.  A single-wave kernel rather than
+// memcpy commands: each runtime copy is its own blit dispatch (3.5-8 us each
+// on the stream).
 __global__ void k_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out) {
   if (threadIdx.x == 0) {
     out->abort = *abort;
-    out->grow = (counters[23] != 0 ? 1 : 0) | (counters[25] != 0 ? 2 : 0);
+    out->grow = (counters[CTR_GROW_HUGE] != 0 ? GROW_HUGE : 0) | (counters[CTR_GROW_CAND] != 0 ? GROW_CAND : 0);
     out->ttotal = *ttotal;
-    out->cnt[0] = counters[0];
-    out->cnt[1] = counters[1];
-    out->cnt[2] = counters[2];
-    out->route_huge = counters[22];
+    out->pool_used = counters[CTR_POOL_USED];
+    out->pool_over = counters[CTR_POOL_OVER];
+    out->route_huge = counters[CTR_ROUTE_HUGE];
   }
 }
-
-// the transition matrices' total (scan of K3's sizes) against the buffer
-__global__ void k_cap_check(DevBatch b, DevWork w) {
-  if (w.trans_off[b.n_points] > w.trans_cap) *w.abort = 1;
-}
-
-
 
 // ============================================================== turn-aware bounded search
 // DESIGN.md §3 rule 4 (oracle ta_search): the route of a transition is the
@@ -1668,31 +1599,24 @@ __device__ __forceinline__ unsigned long long word64(int lo, int hi) {
 // trips (point -> previous column -> candidates -> rows -> slots), so several
 // columns per wave multiply the misses in flight at the same occupancy.
 // The front of the chain (column record, candidates, rows) runs per group; the
-// pairs of the wave's columns are then taken by all 64 lanes (OTM_TRANS_FLAT
-// below).  Columns the index
+// pairs of the wave's columns are then taken by all 64 lanes (the flat pair
+// loop below).  Columns the index
 // cannot answer (cost bound > the index's, a source row incomplete, more than
-// KC candidates) go to the search tiers (w.overflow_list0, count
-// w.counters_i32[4]).
+// KC candidates) go to the search tiers (CTR_INDEX_MISS).
 // At 8 lanes per column (8 columns per wave) a column with more than
 // OTM_TRANS_KC8 candidates on either side goes to the wide list
-// (w.overflow_list2, count w.counters_i32[6]), which a 16-lane pass (LIST)
+// (CTR_TRANS_WIDE), which a 16-lane pass (LIST)
 // then answers from the index; KC8 keeps the LDS words within 8 waves per SIMD.
 #ifndef OTM_TRANS_KC8
 #define OTM_TRANS_KC8 8
 #endif
-// The pair loop.  OTM_TRANS_FLAT=1: the pairs of the wave's NS columns are laid
-// end to end and lane L takes flat pairs L, L + 64, ...: ceil(sum / 64) probe
-// steps per wave, where each group looping over its own column (=0, the
-// earlier form, kept for A/B builds) takes as many as the wave's largest
-// column, ceil(max / S), with the smaller columns' lanes idle.  The front
-// phase stays per group; each pair's arithmetic, probes and stored float are
-// the same in both forms.
-#ifndef OTM_TRANS_FLAT
-#define OTM_TRANS_FLAT 1
-#endif
-#if OTM_TRANS_FLAT && OTM_TRANS_BATCH != 1
-#error "the flat pair loop takes one pair per lane per step (OTM_TRANS_BATCH=1)"
-#endif
+// The pair loop is flat: the pairs of the wave's NS columns are laid end to
+// end and lane L takes flat pairs L, L + 64, ...: ceil(sum / 64) probe steps
+// per wave, where each group looping over its own column (the earlier form)
+// took as many as the wave's largest column, ceil(max / S), with the smaller
+// columns' lanes idle.  The front phase stays per group; each pair's
+// arithmetic, probes and stored float are those of the earlier form
+// (DESIGN.md §5 K4).
 // waves per SIMD the register budget is sized for
 #ifndef OTM_TRANS_WAVES
 #define OTM_TRANS_WAVES 8
@@ -1708,12 +1632,10 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
   __shared__ int4 tg[NS][KC];  // target: edge, offset bits, label key, -
   __shared__ int4 sr[NS][KC];  // source: edge, offset bits, remaining-length bits, end heading
   __shared__ IdxRow rq[NS][KC];
-#if OTM_TRANS_FLAT
   // a column group's record for the flat pair loop, left by its first lane:
   // {trans offset lo, hi, Kp | Kq << 8 | active << 16, gcv}, {bound, cq, the
   // probed index level's slots lo, hi}
   __shared__ int4 cr[NS][2];
-#endif
   // slot of candidate k in its column group's row: XOR-swizzled so that the
   // groups a ds_read_b128 lane group spans (MI355X_MICROARCH.md §LDS: lanes
   // {0-3,12-15,20-27}, ...) read different banks when they read the same k
@@ -1721,12 +1643,9 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
   // 64 banks; at 16 lanes, every row spans all 64).  Kept under the flat pair
   // loop, where a column's reads come from consecutive lanes instead: config 2
   // 181.2 us with it, 183.6 without (profiles/trans_flat/knobs.json)
-#ifndef OTM_TRANS_SWZ
-#define OTM_TRANS_SWZ 1
-#endif
   const int lane = threadIdx.x, sg = lane / S, sl = lane % S;
   const unsigned long long smask = ((1ull << S) - 1ull) << (sg * S);
-  const int swz = !OTM_TRANS_SWZ ? 0 : (S == 8 ? ((sg >> 1) & 1) * 4 : (sg & 1) * 8);
+  const int swz = S == 8 ? ((sg >> 1) & 1) * 4 : (sg & 1) * 8;
   const DevIndex& X = w.idx;
   unsigned long long c_search = 0, c_settled = 0, c_relaxed = 0, c_trans = 0;
   const bool ordered = !LIST && (P.order_mask & ORDER_TRANS) != 0;
@@ -1760,7 +1679,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
   int64_t base, end, stride;
   if (LIST) {
     base = (int64_t)blockIdx.x * NS;
-    end = w.counters_i32[6];
+    end = w.counters_i32[CTR_TRANS_WIDE];
     stride = (int64_t)gridDim.x * NS;
   } else if (ordered) {
     const int grp = blockIdx.x % ORDER_GROUPS;
@@ -1791,7 +1710,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
       Kp = A.z >> 8;
       gcv = __int_as_float(A.w);
     } else if (act) {
-      p = LIST ? (int64_t)w.overflow_list2[it] : (ordered ? (int64_t)w.ord.item[it] : it);
+      p = LIST ? (int64_t)spill_list<CTR_TRANS_WIDE>(w)[it] : (ordered ? (int64_t)w.ord.item[it] : it);
       q = w.col_prev[p];
       Kq = w.kq_prev[p];
       Kp = w.ncand[p];
@@ -1803,25 +1722,17 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
     const uint32_t cq = index_cost_bound(bound);
     const bool idx_ok = X.rmax > 0.0f && cq <= X.cmax;
     // the near index when it covers the bound (same answers, smaller tables)
-#if OTM_SRC_REC
     const SrcRec* xsrc = X.src;
-#else
-    const IdxRow* xrow = X.row;
-#endif
     const uint4* xslot = X.slot;
 #pragma unroll
     for (int l = NEAR_LEVELS - 1; l >= 0; --l) {
       if (w.idxn[l].rmax > 0.0f && cq <= w.idxn[l].cmax) {
-#if OTM_SRC_REC
         xsrc = w.idxn[l].src;
-#else
-        xrow = w.idxn[l].row;
-#endif
         xslot = w.idxn[l].slot;
       }
     }
     const bool wide = WIDE && act && idx_ok && (Kp > KC || Kq > KC);
-    if (wide && sl == 0) w.overflow_list2[atomicAdd(&w.counters_i32[6], 1)] = (int32_t)p;
+    if (wide && sl == 0) spill_push<CTR_TRANS_WIDE>(w, (int32_t)p);
     act = act && !wide;
     bool bad = act && (!idx_ok || Kp > KC || Kq > KC);
     // candidates of p (targets) and of q (sources), then rows
@@ -1838,8 +1749,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
         const int32_t e = c.x;
         const float o = __int_as_float(c.y);
         // src_start and src_row from the edge's {from, length} pair (one
-        // load); the heading only for the work counters (no load otherwise)
-#if OTM_SRC_REC
+        // load); the heading only for the work counters (no load otherwise);
         // with an index, both out of the edge's source record: the row that
         // cand_node(o) selects and the length, addressed by the candidate
         // record alone, leave together (the row's number needed from(e) first)
@@ -1857,25 +1767,11 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
           rq[sg][k ^ swz] = R;
           bad = bad || R.cnt < 0;
         }
-#else
-        const int2 fl = g.e_fl[e];
-        const float start = cand_node(o) ? 0.0f : __int_as_float(fl.y) - o;
-        sr[sg][k ^ swz] = make_int4(e, __float_as_int(o), __float_as_int(start), w.ctr ? (int)src_head(g, e, o) : 0);
-        if (idx_ok) {
-          const IdxRow R = xrow[cand_node(o) ? (int64_t)g.n_edges + fl.x : (int64_t)e];
-          rq[sg][k ^ swz] = R;
-          bad = bad || R.cnt < 0;
-        }
-#endif
       }
     }
     const bool spill = (__ballot(bad) & smask) != 0ull;
-    if (spill && act && sl == 0) {
-      const int slot = atomicAdd(&w.counters_i32[4], 1);
-      w.overflow_list0[slot] = (int32_t)p;
-    }
+    if (spill && act && sl == 0) spill_push<CTR_INDEX_MISS>(w, (int32_t)p);
     act = act && !spill;
-#if OTM_TRANS_FLAT
     // an inactive group (out of range, unlinked, wide-listed, spilled) has no pairs
     const int npair_g = act ? Kq * Kp : 0;
     if (sl == 0) {
@@ -1906,7 +1802,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
           }
         }
         const int idx = f - pc;
-        const int cz = !OTM_TRANS_SWZ ? 0 : (S == 8 ? ((c >> 1) & 1) * 4 : (c & 1) * 8);
+        const int cz = S == 8 ? ((c >> 1) & 1) * 4 : (c & 1) * 8;
         const int4 C0 = cr[c][0], C1 = cr[c][1];
         const int kp = C0.z & 255;
         const float gcv_c = __int_as_float(C0.w), bound_c = __int_as_float(C1.x);
@@ -1965,86 +1861,6 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
         c_trans += ntr;
       }
     }
-#else
-    wave_sync();
-    if (act) {
-      float* Tm = w.trans + toff;
-      unsigned long long ntr = 0;
-      // OTM_TRANS_BATCH pairs per lane per step: every pair's first bucket
-      // (two slots, one aligned 32-B piece of a line) is loaded before any is
-      // resolved, so their probes are in flight together
-      constexpr int NB = OTM_TRANS_BATCH;
-      const int npair = Kq * Kp;
-      for (int idx0 = sl; idx0 < npair; idx0 += S * NB) {
-        uint4 s0[NB], s1[NB];
-        uint32_t h0[NB];
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-          const int idx = idx0 + u * S;
-          s0[u] = make_uint4(EMPTY, 0u, 0u, 0u);
-          s1[u] = s0[u];
-          h0[u] = 0u;
-          if (idx < npair) {
-            const int i = idx / Kp, j = idx - (idx / Kp) * Kp;
-            const int4 T = tg[sg][j ^ swz], Sx = sr[sg][i ^ swz];
-            const IdxRow R = rq[sg][i ^ swz];
-            const bool same = same_edge_step(Sx.x, __int_as_float(Sx.y), T.x, __int_as_float(T.y));
-            if (!same && R.cnt > 0) {
-              h0[u] = idx_slot0((uint32_t)T.w, R);
-              s0[u] = xslot[R.off + h0[u]];
-              s1[u] = xslot[R.off + h0[u] + 1];
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-          const int idx = idx0 + u * S;
-          if (idx >= npair) continue;
-          const int i = idx / Kp, j = idx - (idx / Kp) * Kp;
-          const int4 T = tg[sg][j ^ swz], Sx = sr[sg][i ^ swz];
-          const uint32_t key = (uint32_t)T.z;
-          const int32_t ej = T.x, ei = Sx.x;
-          const float oj = __int_as_float(T.y), oi = __int_as_float(Sx.y), si = __int_as_float(Sx.z);
-          float r = 0.0f;
-          bool ok = true;
-          uint32_t units = 0;
-          if (same_edge_step(ei, oi, ej, oj)) {
-            r = same_edge_dist(oi, oj);
-          } else {
-            const IdxRow R = rq[sg][i ^ swz];
-            uint4 sv = s0[u];
-            if (R.cnt > 0 && sv.x != key && sv.x != EMPTY) {
-              sv = s1[u];
-              uint32_t h = h0[u] + 1u;
-              while (sv.x != key && sv.x != EMPTY) {  // the rest of the linear probe (rare)
-                h = idx_next(h, R);
-                sv = xslot[R.off + h];
-              }
-            }
-            // a label of the row beyond this column's cost bound is not one
-            // of its search's labels
-            if (R.cnt > 0 && sv.x == key && idx_slot_cost(sv) <= cq) {
-              const float sd = si + bitsf(sv.z);
-              r = sd + oj;
-              units = idx_slot_units(sv);
-            } else {
-              ok = false;
-            }
-          }
-          float cost = INFINITY;
-          if (ok && r <= bound) {
-            cost = trans_cost(units, r, gcv, P.beta);
-            ++ntr;
-          }
-          Tm[i * Kp + j] = cost;
-        }
-      }
-      if (w.ctr) {
-        count_searches(Kq, cq, xslot);
-        c_trans += ntr;
-      }
-    }
-#endif
     wave_sync();
   }
   if (w.ctr) {
@@ -2119,7 +1935,6 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
     for (int l = NEAR_LEVELS - 1; l >= 0; --l)
       if (w.idxn[l].rmax > 0.0f && cq <= w.idxn[l].cmax) lvl = l;
     const DevIndex& Xc = lvl >= 0 ? w.idxn[lvl] : X;
-#if OTM_SRC_REC
     // the source's row and length out of its edge's source record: the row's
     // address from the chosen candidate alone, the length beside it
     int32_t leni = 0;
@@ -2128,27 +1943,17 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
       leni = Xc.src[ei].len;
       sv = idx_find(Xc.slot, Rw, dst_key(g, ej, oj), lab);
     }
-#else
-    // the source's row and start from its edge's {from, length} pair (one load)
-    const int2 fli = g.e_fl[ei];
-    const int32_t leni = fli.y;
-    if (X.rmax > 0.0f && cq <= X.cmax) {
-      Rw = Xc.row[cand_node(oi) ? (int64_t)g.n_edges + fli.x : (int64_t)ei];
-      sv = idx_find(Xc.slot, Rw, dst_key(g, ej, oj), lab);
-    }
-#endif
     if (sv < 0 || idx_slot_cost(lab) > cq) {
-      const int slot = atomicAdd(&w.counters_i32[4], 1);
-      w.overflow_list0[slot] = (int32_t)p;
+      spill_push<CTR_INDEX_MISS>(w, (int32_t)p);
       continue;
     }
     // the path: the label's predecessor slots in the row, back to the first
     // edge (a slot holds its label's edge and its predecessor's slot)
     int len = 0;
     for (int32_t ps = idx_slot_pred(lab); ps >= 0 && len <= Rw.cnt; ps = idx_slot_pred(Xc.slot[Rw.off + ps])) ++len;
-    const int off = len ? atomicAdd(&w.counters_i32[1], len) : 0;
+    const int off = len ? atomicAdd(&w.counters_i32[CTR_POOL_USED], len) : 0;
     if (off + len > w.pool_cap) {
-      w.counters_i32[2] = 1;
+      w.counters_i32[CTR_POOL_OVER] = 1;
       *w.abort = 1;
       w.path_len[p] = -1;
     } else {
@@ -2190,10 +1995,10 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
 }
 
 // ============================================================== K4 transitions (wave tiers)
-// Columns the index tier could not answer (list in w.overflow_list0, count in
-// w.counters_i32[4], read on the device: no host round trip): one turn-aware
+// Columns the index tier could not answer (CTR_INDEX_MISS, list and count
+// read on the device: no host round trip): one turn-aware
 // search per distinct source (node, heading), the wave's table in LDS.  The
-// LDS tier spills to `w.overflow_list2` / counters_i32[3], which the
+// LDS tier spills to CTR_SEARCH_GLOBAL, which the
 // global-memory tier (BIG) drains.
 // the search table of a tier's block: LDS (0), global (1), huge (2)
 template <int TIER>
@@ -2224,7 +2029,7 @@ __device__ __forceinline__ bool huge_unready(DevWork& w, int64_t nwork, const in
     for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < nwork; it += (int64_t)gridDim.x * blockDim.x)
       atomicCAS(&w.trace_err[w.pt_trace[list[it]]], 0, OTM_TERR_SEARCH_OVERFLOW);
   } else if (blockIdx.x == 0 && threadIdx.x == 0) {
-    w.counters_i32[23] = 1;
+    w.counters_i32[CTR_GROW_HUGE] = 1;
     *w.abort = 1;
   }
   return true;
@@ -2235,14 +2040,14 @@ __device__ __forceinline__ void huge_overflow(DevWork& w, int64_t p) {
   if (w.huge_final) {
     atomicCAS(&w.trace_err[w.pt_trace[p]], 0, OTM_TERR_SEARCH_OVERFLOW);
   } else {
-    w.counters_i32[23] = 1;  // the huge tables are too small: grow, redo
+    w.counters_i32[CTR_GROW_HUGE] = 1;  // the huge tables are too small: grow, redo
     *w.abort = 1;
   }
 }
 
 // TIER 0: LDS tables; 1: global tables (BIG_SLOTS x BIG_TABLE_CAP); 2: the
-// huge tier (HUGE_SLOTS x 2^huge_log2).  Spills: 0 -> list2 ([3]) -> 1 ->
-// list3 ([21]) -> 2 -> the host grows the huge tables and redoes the batch.
+// huge tier (HUGE_SLOTS x 2^huge_log2).  Spills: 0 -> CTR_SEARCH_GLOBAL -> 1 ->
+// CTR_TRANS_HUGE -> 2 -> the host grows the huge tables and redoes the batch.
 template <int TIER>
 __global__ __launch_bounds__(TB) void k_transitions(DevGraph g, DevBatch b, DevParams P, DevWork w) {
   constexpr bool BIG = TIER > 0;
@@ -2264,9 +2069,10 @@ __global__ __launch_bounds__(TB) void k_transitions(DevGraph g, DevBatch b, DevP
     const int sx = table_find<BIG>(T, e);
     return sx < 0 ? NONE_PRED : (uint32_t)(Mem<BIG>::ld(&T.lab[sx]) & 0xFFFFFFFFull);
   };
-  const int32_t* list = TIER == 2 ? w.overflow_list3 : (BIG ? w.overflow_list2 : w.overflow_list0);
-  const int64_t nwork = TIER == 2 ? (int64_t)w.counters_i32[21]
-                                  : (BIG ? (int64_t)w.counters_i32[3] : (int64_t)w.counters_i32[4]);
+  const SpillRef work = TIER == 2 ? spill_of<CTR_TRANS_HUGE>(w)
+                                  : (BIG ? spill_of<CTR_SEARCH_GLOBAL>(w) : spill_of<CTR_INDEX_MISS>(w));
+  const int32_t* list = work.list;
+  const int64_t nwork = (int64_t)*work.count;
   if (TIER == 2 && huge_unready(w, nwork, list)) return;
   __syncthreads();
   for (int64_t it = blockIdx.x; it < nwork; it += gridDim.x) {
@@ -2364,9 +2170,9 @@ __global__ __launch_bounds__(TB) void k_transitions(DevGraph g, DevBatch b, DevP
     }
     if (failed && lane == 0) {
       if (TIER == 0) {
-        w.overflow_list2[atomicAdd(&w.counters_i32[3], 1)] = (int32_t)p;
+        spill_push<CTR_SEARCH_GLOBAL>(w, (int32_t)p);
       } else if (TIER == 1) {
-        w.overflow_list3[atomicAdd(&w.counters_i32[21], 1)] = (int32_t)p;
+        spill_push<CTR_TRANS_HUGE>(w, (int32_t)p);
       } else {
         huge_overflow(w, p);
       }
@@ -2510,7 +2316,7 @@ __global__ __launch_bounds__(TB, OTM_VIT_WAVES) void k_viterbi(DevBatch b, DevWo
                                                                const int32_t* list_n, int snap) {
   // spill snapshot B: columns per transition tier (Viterbi does not touch the
   // counters; they start over for the route tiers)
-  if (OTM_FOLD_BOOKKEEPING && snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, 1, true);
+  if (snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, SNAP_AFTER_TRANS, true);
   if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
   __shared__ float sT[VIT_TW];
   __shared__ float sEm[VIT_EW];
@@ -2831,7 +2637,7 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
   constexpr int CH = OTM_VG_CHUNK;  // points per chunk (<= G)
   static_assert(CH <= G, "a chunk's metadata is one byte per lane");
   // spill snapshot B (see k_viterbi)
-  if (OTM_FOLD_BOOKKEEPING && snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, 1, true);
+  if (snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, SNAP_AFTER_TRANS, true);
   if (*w.abort) return;
   // group rows padded by G words: group g's row starts g x G banks on, so the
   // wave's 64 lanes staging (or reading) the same offset j of their groups'
@@ -3217,7 +3023,7 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
   static_assert(CH >= 1 && CH <= G && U >= 4 && U % 4 == 0, "chunk knobs");
   static_assert(RS % 4 == 0, "a row's window is staged by 16-byte stores");
   // spill snapshot B (see k_viterbi)
-  if (OTM_FOLD_BOOKKEEPING && snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, 1, true);
+  if (snap && blockIdx.x == 0 && threadIdx.x == 0) fold_snap(w, SNAP_AFTER_TRANS, true);
   if (*w.abort) return;
   // the rows' windows, then G x G floats that stay +inf: a masked source's
   // read (up to 255 floats past a block's start) stays inside
@@ -3543,9 +3349,9 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
 }
 
 // ============================================================== K6 route
-// Steps the index tier could not answer (w.overflow_list0 / counters_i32[4]):
+// Steps the index tier could not answer (CTR_INDEX_MISS):
 // the winning search again, its target label's predecessor chain as the path.
-// TIER as k_transitions (spill lists: list0 [4] -> list2 [3] -> list3 [22])
+// TIER as k_transitions (spills: CTR_INDEX_MISS -> CTR_SEARCH_GLOBAL -> CTR_ROUTE_HUGE)
 template <int TIER>
 __global__ __launch_bounds__(TB) void k_route(DevGraph g, DevBatch b, DevParams P, DevWork w) {
   constexpr bool BIG = TIER > 0;
@@ -3565,9 +3371,10 @@ __global__ __launch_bounds__(TB) void k_route(DevGraph g, DevBatch b, DevParams 
     const int sx = table_find<BIG>(T, e);
     return sx < 0 ? NONE_PRED : (uint32_t)(Mem<BIG>::ld(&T.lab[sx]) & 0xFFFFFFFFull);
   };
-  const int32_t* list = TIER == 2 ? w.overflow_list3 : (BIG ? w.overflow_list2 : w.overflow_list0);
-  const int64_t nwork = TIER == 2 ? (int64_t)w.counters_i32[22]
-                                  : (BIG ? (int64_t)w.counters_i32[3] : (int64_t)w.counters_i32[4]);
+  const SpillRef work = TIER == 2 ? spill_of<CTR_ROUTE_HUGE>(w)
+                                  : (BIG ? spill_of<CTR_SEARCH_GLOBAL>(w) : spill_of<CTR_INDEX_MISS>(w));
+  const int32_t* list = work.list;
+  const int64_t nwork = (int64_t)*work.count;
   if (TIER == 2 && huge_unready(w, nwork, list)) return;
   __syncthreads();
   for (int64_t it = blockIdx.x; it < nwork; it += gridDim.x) {
@@ -3588,9 +3395,9 @@ __global__ __launch_bounds__(TB) void k_route(DevGraph g, DevBatch b, DevParams 
     if (labels < 0) {
       if (lane == 0) {
         if (TIER == 0) {
-          w.overflow_list2[atomicAdd(&w.counters_i32[3], 1)] = (int32_t)p;
+          spill_push<CTR_SEARCH_GLOBAL>(w, (int32_t)p);
         } else if (TIER == 1) {
-          w.overflow_list3[atomicAdd(&w.counters_i32[22], 1)] = (int32_t)p;
+          spill_push<CTR_ROUTE_HUGE>(w, (int32_t)p);
         } else {
           huge_overflow(w, p);
         }
@@ -3612,9 +3419,9 @@ __global__ __launch_bounds__(TB) void k_route(DevGraph g, DevBatch b, DevParams 
         uint32_t units;
         int n;
         chain_sums(g, TU, predof, pk, hin, NO_HEAD, cbuf, d, units, n);
-        const int off = atomicAdd(&w.counters_i32[1], n);
+        const int off = atomicAdd(&w.counters_i32[CTR_POOL_USED], n);
         if (off + n > w.pool_cap) {
-          w.counters_i32[2] = 1;
+          w.counters_i32[CTR_POOL_OVER] = 1;
           *w.abort = 1;
           w.path_len[p] = -1;
         } else {
@@ -4534,14 +4341,11 @@ __device__ __forceinline__ bool in_lv(const int64_t* lv, int n, int64_t x) {
 #ifndef OTM_REPORT_WAVES
 #define OTM_REPORT_WAVES 1
 #endif
-// report() launch: 1 = a wave per trace over an LDS copy of its segments
-// (k_report_wave), 0 = a thread per trace (k_report), 2 = the wave form up to
-// REPW_MAX_TRACES traces (two rounds of 8 waves per SIMD), else the thread
-// form.  Measured: config 2 (10k traces) 0.0445 -> 0.0392 ms with the wave
-// form; config 4 (100k traces) 0.106 -> 0.290 ms, so it is not used there.
-#ifndef OTM_REPORT_FORM
-#define OTM_REPORT_FORM 2
-#endif
+// report() launch: a wave per trace over an LDS copy of its segments
+// (k_report_wave) up to REPW_MAX_TRACES traces (two rounds of 8 waves per
+// SIMD), else a thread per trace (k_report).  Measured: config 2 (10k traces)
+// 0.0445 -> 0.0392 ms with the wave form; config 4 (100k traces) 0.106 ->
+// 0.290 ms, so it is not used there.
 constexpr int32_t REPW_MAX_TRACES = 2 * 8 * 4 * 256;
 // report() (py/reporter_service.py:110-215) over one trace's segments, one
 // thread per trace.  Segment times are Python values: a segment without
@@ -4689,8 +4493,8 @@ __device__ __forceinline__ void report_pass(const DevOut& o, int32_t seg_off, in
   if (o.pairs.key) report_pair(o, seg_off, seg_cnt, ps, rep);
 }
 
-// report() (py/reporter_service.py:110-215), one thread per trace (the
-// OTM_REPORT_FORM 0 launch).
+// report() (py/reporter_service.py:110-215), one thread per trace (batches
+// of more than REPW_MAX_TRACES traces).
 __global__ __launch_bounds__(256, OTM_REPORT_WAVES) void k_report(DevBatch b, DevReportCfg rc, DevWork w, DevOut o, int32_t n_seg_total) {
   if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
   const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4834,7 +4638,7 @@ __device__ float interp_pos(const DevGraph& g, const DevBatch& b, const DevParam
 __global__ __launch_bounds__(256) void k_seg_bound(DevGraph g, DevBatch b, DevParams P, DevWork w, int64_t* tb) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // spill snapshot C: steps per route tier (kept for the status read)
-  if (OTM_FOLD_BOOKKEEPING && k == b.n_points) fold_snap(w, 2, false);
+  if (k == b.n_points) fold_snap(w, SNAP_AFTER_ROUTE, false);
   if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
   const int lane = threadIdx.x & 63;
   int64_t v = 0;
@@ -5252,12 +5056,6 @@ void launch_links(const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t
   TIMED(KN_LINKS, hipLaunchKernelGGL(k_links, dim3(grid_for(b.n_points + 1, 256, 1 << 30)), dim3(256), 0, s, b, p,
                                      w));
 }
-void launch_batch_init(int32_t* counters, int32_t* abort, hipStream_t s) {
-  hipLaunchKernelGGL(k_batch_init, dim3(1), dim3(64), 0, s, counters, abort);
-}
-void launch_snap(int32_t* counters, int32_t* snap, bool reset, hipStream_t s) {
-  hipLaunchKernelGGL(k_snap, dim3(1), dim3(64), 0, s, counters, snap, reset ? 1 : 0);
-}
 // The compact host batch (otm_match_compact) widened on the device: a wave per
 // trace, its points' time = base + delta (whole seconds, exact in a double)
 // and accuracy as float -- the arrays every stage reads.
@@ -5282,10 +5080,6 @@ void launch_expand_compact(const int64_t* trace_off, const int64_t* tbase, const
 void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out,
                    hipStream_t s) {
   hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, s, abort, ttotal, counters, out);
-}
-bool fold_bookkeeping() { return OTM_FOLD_BOOKKEEPING != 0; }
-void launch_cap_check(const DevBatch& b, DevWork& w, hipStream_t s) {
-  hipLaunchKernelGGL(k_cap_check, dim3(1), dim3(1), 0, s, b, w);
 }
 void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
                         const Marks& mk, int sub, int from) {
@@ -5338,10 +5132,13 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   // 76 + 5 at 4,096, 123 against 84 + 5 at 8,192)
   constexpr int rmin = 4096;
   const int form = forced ? forced : (b.n_traces >= gmin ? 8 : (b.n_traces >= rmin ? 4 : 64));
+  // what a form cannot take goes down a list to the next one (kernels.h: both
+  // lists are free between the transition and route stages, K1 zeroes the counts)
+  const SpillRef to_16 = spill_of<CTR_VIT_16>(w), to_wave = spill_of<CTR_VIT_WAVE>(w);
   if (form == 4) {
     // the row form (k_viterbi_row: four traces per wave) over every trace;
     // what it cannot take (more than VR_PTS points, a column wider than 16
-    // candidates) to the wave form, through overflow_list2 / [26] as below.
+    // candidates) to the wave form, through the CTR_VIT_WAVE list as below.
     // OTM_VR_WIN: the window's floats a chunk may use (the tests force the
     // per-step path with a small one)
     const char* we = std::getenv("OTM_VR_WIN");
@@ -5353,11 +5150,11 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
     const int fast = fa ? (std::atoi(fa) != 0 ? 1 : 0) : 1;
     mk.begin(KN_VITERBI, s);
     hipLaunchKernelGGL(k_viterbi_row, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
-                       w.overflow_list2, w.counters_i32 + 26, win, fast, 1);
+                       to_wave.list, to_wave.count, win, fast, 1);
     // (sized for every trace, as a batch of long traces needs: a block whose
     // list entries ran out exits at once)
     hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
-                       (const int32_t*)w.overflow_list2, (const int32_t*)(w.counters_i32 + 26), 0);
+                       (const int32_t*)to_wave.list, (const int32_t*)to_wave.count, 0);
     mk.end(KN_VITERBI, s);
     return;
   }
@@ -5368,13 +5165,11 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   }
   // 8 lanes per trace over every trace; what it cannot take (a column wider
   // than 8 candidates, more than VG_PTS points) to 16 lanes per trace; what
-  // that cannot take to the wave-per-trace form.  Lists: overflow_list0 (count
-  // counters_i32[20]) and overflow_list2 ([26]), both free between the
-  // transition and route stages; the counts are zeroed by K1.
-  int32_t* l8 = w.overflow_list0;
-  int32_t* n8 = w.counters_i32 + 20;
-  int32_t* l16 = w.overflow_list2;
-  int32_t* n16 = w.counters_i32 + 26;
+  // that cannot take to the wave-per-trace form.
+  int32_t* l8 = to_16.list;
+  int32_t* n8 = to_16.count;
+  int32_t* l16 = to_wave.list;
+  int32_t* n16 = to_wave.count;
   mk.begin(KN_VITERBI, s);
   if (form == 16) {
     hipLaunchKernelGGL(k_viterbi_g<16>, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
@@ -5406,14 +5201,13 @@ void launch_route(const DevGraph& g, const DevBatch& b, const DevParams& p, DevW
   hipLaunchKernelGGL(k_route<2>, dim3(HUGE_SLOTS), dim3(TB), 0, s, g, b, p, w);
   mk.end(KN_ROUTE_GLOBAL, s);
 }
-void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, bool write, hipStream_t s,
-                     const Marks& mk) {
-  (void)write;
+void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk) {
   const dim3 grid(grid_for(b.n_traces, 1, WAVE_GRID_CAP));
   // small LDS plan over every trace, the large one over its spills
-  // (list in overflow_list0, count in counters_i32[8]: free after the route stage)
-  int32_t* lst = w.overflow_list0;
-  int32_t* cnt = w.counters_i32 + 8;
+  // (CTR_SEG_LARGE: its list is free after the route stage)
+  const SpillRef large = spill_of<CTR_SEG_LARGE>(w);
+  int32_t* lst = large.list;
+  int32_t* cnt = large.count;
   mk.begin(KN_SEG_WRITE, s);
   hipLaunchKernelGGL((k_segments<SEGP_PTS_S, SEGP_TRAV_S>), grid, dim3(TB), 0, s, g, b, w, o, (const int32_t*)nullptr,
                      (const int32_t*)nullptr, lst, cnt);
@@ -5446,7 +5240,7 @@ void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut
   // blocks spread the traces over more waves (0.053 -> 0.050 ms against 64 on
   // config 2)
   constexpr int tb = 16;
-  if (OTM_REPORT_FORM == 1 || (OTM_REPORT_FORM == 2 && b.n_traces <= REPW_MAX_TRACES))
+  if (b.n_traces <= REPW_MAX_TRACES)
     TIMED(KN_REPORT, hipLaunchKernelGGL(k_report_wave, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s,
                                         b, rc, w, o, 0));
   else

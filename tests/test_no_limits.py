@@ -169,6 +169,21 @@ def _gpu_vs_oracle(graph, b, meili, oracle, results_equal):
     return first, second
 
 
+# otm_spill_stats of the two batches below, as commit 93c84c5 (the last before
+# the counter slots got names) reported them on an MI355X: the same in two runs
+# of it, for both path kinds, and for the first and the second match of a
+# batch.  The inputs are seeded and the tiers' work is a function of them, so
+# equality is the check: it pins which slot and snapshot each field reads.
+STAR_SPILLS = dict(cand_wave=14, trans_online=11, trans_wave=11, trans_global=11, route_online=1, route_wave=1,
+                   route_global=1, cand_big=14, trans_huge=0, route_huge=0)
+GRID_SPILLS = dict(cand_wave=18, trans_online=15, trans_wave=15, trans_global=15, route_online=15, route_wave=15,
+                   route_global=15, cand_big=0, trans_huge=9, route_huge=9)
+
+
+def _spills_equal(got, want):
+    assert {k: got[k] for k in want} == want
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("path_kind", ["large", "small"])
 def test_gpu_star_candidate_hbm_tier(star, oracle, results_equal, monkeypatch, path_kind):
@@ -182,6 +197,8 @@ def test_gpu_star_candidate_hbm_tier(star, oracle, results_equal, monkeypatch, p
     # 6); a transition-matrix overflow in the same batch still redoes it whole
     assert first["resumed"] >= 1 and second["resumed"] == 0
     assert second["cand_wave"] == first["cand_wave"]  # the spill snapshots survive the resume
+    _spills_equal(first, STAR_SPILLS)
+    _spills_equal(second, STAR_SPILLS)
 
 
 @pytest.mark.gpu
@@ -196,6 +213,8 @@ def test_gpu_long_gaps_huge_search_tier(dense_grid, oracle, results_equal):
     for k in ("cand_wave", "trans_online", "trans_global", "route_online", "route_global", "trans_huge",
               "route_huge"):
         assert first[k] == second[k], k
+    _spills_equal(first, GRID_SPILLS)
+    _spills_equal(second, GRID_SPILLS)
 
 
 @pytest.mark.gpu
