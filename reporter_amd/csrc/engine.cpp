@@ -25,63 +25,13 @@ namespace otm {
     }                                                                          \
   } while (0)
 
-static int ensure(otm_engine::Buf& b, size_t bytes, std::string* err);
+// a step that returns OTM_OK or an error code (message in *err)
+#define TRY(x)                    \
+  do {                            \
+    if (int rc_ = (x)) return rc_; \
+  } while (0)
+
 static void pairs_drop(otm_engine* M);
-// host-pinned buffer of at least `bytes` (contents not kept on growth)
-static int ensure_pinned(otm_engine::Buf& b, size_t bytes, std::string* err) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return OTM_OK;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  const size_t want = bytes + bytes / 4;
-  HIPCHK(hipHostMalloc(&b.p, want, hipHostMallocDefault));
-  b.cap = want;
-  return OTM_OK;
-}
-#define ENS_F(buf, bytes) \
-  if ((rc = ensure(E->buf, (bytes), err))) return rc;
-
-static int ensure(otm_engine::Buf& b, size_t bytes, std::string* err) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return OTM_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  size_t want = bytes + bytes / 4;  // headroom against regrowth
-  HIPCHK(hipMalloc(&b.p, want));
-  b.cap = want;
-  return OTM_OK;
-}
-
-// Grows an on-demand tier's table (the huge search and candidate tiers): the
-// new allocation first, so that running out of HBM keeps the old table, and
-// the failed hipMalloc's error taken off the runtime so the batch's later
-// hipGetLastError checks do not report it.  OTM_TEST_GROW_OOM (tests only)
-// asks for a size no device has, to drive that path for real.
-static int ensure_grow(otm_engine::Buf& b, size_t bytes, std::string* err) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return OTM_OK;
-  size_t want = bytes + bytes / 4;
-  const char* oom = std::getenv("OTM_TEST_GROW_OOM");
-  if (oom && *oom && *oom != '0') want = (size_t)1 << 62;
-  void* p = nullptr;
-  const hipError_t e = hipMalloc(&p, want);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *err = std::string("hipMalloc (tier table): ") + hipGetErrorString(e);
-    return OTM_EDEVICE;
-  }
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.cap = want;
-  return OTM_OK;
-}
-
-template <class T>
-static T* P(otm_engine::Buf& b) {
-  return (T*)b.p;
-}
 
 // A batch's host waits.  Large batches block on an event, so the waiting
 // thread sleeps instead of spinning: with several batch contexts in flight
@@ -157,8 +107,7 @@ static int auto_grid_mult(const otm_engine* E) {
 
 
 int engine_init(otm_engine* E, const char* graph_path, int device, std::string* err) {
-  int rc = load_graph(graph_path, &E->host, err);
-  if (rc) return rc;
+  TRY(load_graph(graph_path, &E->host, err));
   if (E->host.h.n_edges >= (1 << 27)) {  // K2's lane-tier entries: edge << 4 below the node flag bit
     *err = "graph: 2^27 or more edges";
     return OTM_EINVAL;
@@ -171,49 +120,44 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
     return OTM_EDEVICE;
   }
   const otmg_header& h = E->host.h;
-  auto up = [&](int sec, const void** dst) -> int {
+  DevGraph& g = E->g;
+  // host data into a new HBM array the engine keeps for its life (graph_allocs):
+  // `alloc` bytes (none: 16), the first `bytes` of them copied; the field's own type
+  auto up = [&](const void* src, size_t bytes, size_t alloc, auto& field) -> int {
     void* d = nullptr;
-    size_t n = h.sec[sec].bytes ? h.sec[sec].bytes : 16;
-    HIPCHK(hipMalloc(&d, n));
-    if (h.sec[sec].bytes) HIPCHK(hipMemcpy(d, E->host.section(sec), h.sec[sec].bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&d, alloc ? alloc : 16));
     E->graph_allocs.push_back(d);
-    *dst = d;
+    if (bytes) HIPCHK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    field = static_cast<typename std::remove_reference<decltype(field)>::type>(d);
     return OTM_OK;
   };
-  DevGraph& g = E->g;
-  const void* tmp;
-#define UP(sec, field, T)                 \
-  if ((rc = up(sec, &tmp))) return rc;    \
-  g.field = (const T*)tmp;
-  UP(OTMG_NODE_LAT, node_lat, float);
-  UP(OTMG_NODE_LON, node_lon, float);
-  UP(OTMG_NODE_OUT_OFF, out_off, int32_t);
-  UP(OTMG_EDGE_FROM, e_from, int32_t);
-  UP(OTMG_EDGE_TO, e_to, int32_t);
-  UP(OTMG_EDGE_LEN, e_len, float);
-  UP(OTMG_EDGE_SHAPE_OFF, e_shape_off, int32_t);
-  UP(OTMG_EDGE_WAY, e_way, int64_t);
-  UP(OTMG_EDGE_SEG, e_seg, int32_t);
-  UP(OTMG_EDGE_SEG_POS, e_seg_pos, int32_t);
-  UP(OTMG_EDGE_FLAGS, e_flags, uint8_t);
-  UP(OTMG_SHAPE_LAT, s_lat, float);
-  UP(OTMG_SHAPE_LON, s_lon, float);
-  UP(OTMG_SHAPE_CUM, s_cum, float);
-  UP(OTMG_SEG_ID, g_id, uint64_t);
-  UP(OTMG_SEG_LEN, g_len, float);
-  UP(OTMG_EDGE_HEAD_OUT, e_head_out, uint16_t);
-  UP(OTMG_EDGE_HEAD_IN, e_head_in, uint16_t);
+#define UP(id, field) \
+  TRY(up(h.sec[id].bytes ? E->host.section(id) : nullptr, h.sec[id].bytes, h.sec[id].bytes, g.field))
+  UP(OTMG_NODE_LAT, node_lat);
+  UP(OTMG_NODE_LON, node_lon);
+  UP(OTMG_NODE_OUT_OFF, out_off);
+  UP(OTMG_EDGE_FROM, e_from);
+  UP(OTMG_EDGE_TO, e_to);
+  UP(OTMG_EDGE_LEN, e_len);
+  UP(OTMG_EDGE_SHAPE_OFF, e_shape_off);
+  UP(OTMG_EDGE_WAY, e_way);
+  UP(OTMG_EDGE_SEG, e_seg);
+  UP(OTMG_EDGE_SEG_POS, e_seg_pos);
+  UP(OTMG_EDGE_FLAGS, e_flags);
+  UP(OTMG_SHAPE_LAT, s_lat);
+  UP(OTMG_SHAPE_LON, s_lon);
+  UP(OTMG_SHAPE_CUM, s_cum);
+  UP(OTMG_SEG_ID, g_id);
+  UP(OTMG_SEG_LEN, g_len);
+  UP(OTMG_EDGE_HEAD_OUT, e_head_out);
+  UP(OTMG_EDGE_HEAD_IN, e_head_in);
 #undef UP
   {
     // turn units per deviation 0..180 degrees for the configured
     // turn_penalty_factor, one small device table
     uint32_t tu[TURN_TABLE];
     for (int d = 0; d < TURN_TABLE; ++d) tu[d] = turn_units(E->mc.turn_penalty_factor, d);
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof tu));
-    HIPCHK(hipMemcpy(d, tu, sizeof tu, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    E->dp.turn_units = (const uint32_t*)d;
+    TRY(up(tu, sizeof tu, sizeof tu, E->dp.turn_units));
   }
   {
     // edge costs of the turn-aware searches: L(e) = round(len(e) x 64), in
@@ -221,11 +165,7 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
     const float* len = (const float*)E->host.section(OTMG_EDGE_LEN);
     std::vector<uint32_t> l64((size_t)h.n_edges + 1, 0u);
     for (int32_t e = 0; e < h.n_edges; ++e) l64[(size_t)e] = (uint32_t)std::floor((double)len[e] * 64.0 + 0.5);
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, l64.size() * 4));
-    HIPCHK(hipMemcpy(d, l64.data(), l64.size() * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.e_len64 = (const uint32_t*)d;
+    TRY(up(l64.data(), l64.size() * 4, l64.size() * 4, g.e_len64));
   }
   {
     // K7's edge record: what the segment pass reads per traversal -- length,
@@ -258,16 +198,8 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
       r[3] = (uint32_t)(std::lower_bound(ways.begin(), ways.end(), way[e]) - ways.begin());
     }
     if (ways.empty()) ways.push_back(0);
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, rec.size() * 4));
-    HIPCHK(hipMemcpy(d, rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.e_rec = (const uint4*)d;
-    d = nullptr;
-    HIPCHK(hipMalloc(&d, ways.size() * 8));
-    HIPCHK(hipMemcpy(d, ways.data(), ways.size() * 8, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.way_tab = (const int64_t*)d;
+    TRY(up(rec.data(), rec.size() * 4, rec.size() * 4, g.e_rec));
+    TRY(up(ways.data(), ways.size() * 8, ways.size() * 8, g.way_tab));
     // {from, length bits} per edge: K4 stages a source candidate's index row
     // (from, for a node candidate) and start (length, for an edge candidate)
     // with one 8-byte load instead of two masked 4-byte ones
@@ -277,11 +209,7 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
       fl2[(size_t)e * 2] = from[e];
       std::memcpy(&fl2[(size_t)e * 2 + 1], &len[e], 4);
     }
-    d = nullptr;
-    HIPCHK(hipMalloc(&d, fl2.size() * 4));
-    HIPCHK(hipMemcpy(d, fl2.data(), fl2.size() * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.e_fl = (const int2*)d;
+    TRY(up(fl2.data(), fl2.size() * 4, fl2.size() * 4, g.e_fl));
   }
   {
     // The grid index of the candidate search.  The file's cells (meili's
@@ -335,16 +263,8 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
     // cell offsets as 32-bit words in HBM: a sparse state-scale grid is
     // ~100M mostly-empty cells, and a probe's row range (2 offsets) then
     // usually sits in one cache line
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, nc * 4));
-    HIPCHK(hipMemcpy(d, c32.data(), nc * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.cell_off = (const uint32_t*)d;
-    d = nullptr;
-    HIPCHK(hipMalloc(&d, ent.size() * 4 + 16));
-    if (!ent.empty()) HIPCHK(hipMemcpy(d, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.cell_ent = (const uint32_t*)d;
+    TRY(up(c32.data(), nc * 4, nc * 4, g.cell_off));
+    TRY(up(ent.data(), ent.size() * 4, ent.size() * 4 + 16, g.cell_ent));
     // per cell entry: the shape segment's endpoints (lat_a, lon_a, lat_b,
     // lon_b), laid out in cell order so a probe's scan of one grid row is
     // one contiguous float4 stream (no edge -> shape indirection)
@@ -360,11 +280,7 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
       geo[q * 4 + 2] = slat[a + 1];
       geo[q * 4 + 3] = slon[a + 1];
     }
-    d = nullptr;
-    HIPCHK(hipMalloc(&d, geo.size() * 4));
-    HIPCHK(hipMemcpy(d, geo.data(), geo.size() * 4, hipMemcpyHostToDevice));
-    E->graph_allocs.push_back(d);
-    g.ent_geo = (const float4*)d;
+    TRY(up(geo.data(), geo.size() * 4, geo.size() * 4, g.ent_geo));
     g.grid_rows = R;
     g.grid_cols = Cn;
     g.cell = h.grid_cell_deg * (double)m;
@@ -382,9 +298,9 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
   }
   g.lat0 = h.grid_lat0;
   g.lon0 = h.grid_lon0;
-  HIPCHK(hipMalloc((void**)&E->ctr, sizeof(DevCounters)));
-  HIPCHK(hipMalloc((void**)&E->ctr_save, sizeof(DevCounters)));
-  HIPCHK(hipMemset(E->ctr, 0, sizeof(DevCounters)));
+  TRY(E->ctr.ensure_exact(1, err));
+  TRY(E->ctr_save.ensure_exact(1, err));
+  HIPCHK(hipMemset(E->ctr.p, 0, sizeof(DevCounters)));
   for (auto& e : E->kev) HIPCHK(hipEventCreate(&e));
   return build_index(E, err);
 }
@@ -441,9 +357,9 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->rc = P->rc;
   C->dp = P->dp;
   C->drc = P->drc;
-  HIPCHK(hipMalloc((void**)&C->ctr, sizeof(DevCounters)));
-  HIPCHK(hipMalloc((void**)&C->ctr_save, sizeof(DevCounters)));
-  HIPCHK(hipMemset(C->ctr, 0, sizeof(DevCounters)));
+  TRY(C->ctr.ensure_exact(1, err));
+  TRY(C->ctr_save.ensure_exact(1, err));
+  HIPCHK(hipMemset(C->ctr.p, 0, sizeof(DevCounters)));
   for (auto& e : C->kev) HIPCHK(hipEventCreate(&e));
   (void)err;
   return OTM_OK;
@@ -495,15 +411,21 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   out = IndexBuilt{};
   const int32_t N = E->g.n_edges + E->g.n_nodes;  // rows
   hipStream_t s = E->stream;
-  int32_t* row_cnt = nullptr;
-  int64_t* row_off = nullptr;
-  IdxRow* rows = nullptr;
-  HIPCHK(hipMalloc(&row_cnt, ((size_t)N + 1) * 4));
-  HIPCHK(hipMalloc(&row_off, ((size_t)N + 1) * 8));
-  HIPCHK(hipMalloc(&rows, ((size_t)N + 1) * sizeof(IdxRow)));
-  size_t tmpb = scan_tmp_bytes(N) + 256;
-  void* tmp = nullptr;
-  HIPCHK(hipMalloc(&tmp, tmpb));
+  // scratch of the build, freed on every way out; the index keeps rows (and
+  // slot and src below), which then go to graph_allocs
+  DevBuf<int32_t> row_cnt_b;
+  DevBuf<int64_t> row_off_b;
+  DevBuf<IdxRow> rows_b;
+  DevBuf<char> tmp_b;
+  const size_t tmpb = scan_tmp_bytes(N) + 256;
+  TRY(row_cnt_b.ensure_exact((size_t)N + 1, err));
+  TRY(row_off_b.ensure_exact((size_t)N + 1, err));
+  TRY(rows_b.ensure_exact((size_t)N + 1, err));
+  TRY(tmp_b.ensure_exact(tmpb, err));
+  int32_t* const row_cnt = row_cnt_b.p;
+  int64_t* const row_off = row_off_b.p;
+  IdxRow* const rows = rows_b.p;
+  void* const tmp = tmp_b.p;
   int64_t total = 0;
   int pct = index_load_fast();
   // the per-edge source records (kernels.h SrcRec) are part of the index: in its budget
@@ -529,33 +451,29 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
     if (need <= (double)budget) break;
     const float rr = (float)(std::floor(*r * std::sqrt((double)budget / need) * 0.9 / 50.0) * 50.0);
     if (!shrink || attempt == 4 || rr < 100.0f) {
-      (void)hipFree(tmp);
-      (void)hipFree(rows);
-      (void)hipFree(row_off);
-      (void)hipFree(row_cnt);
       *r = 0.0f;  // no index
       return OTM_OK;
     }
     *r = rr;
   }
-  (void)hipFree(tmp);
-  E->graph_allocs.push_back(row_cnt);
-  E->graph_allocs.push_back(row_off);
-  E->graph_allocs.push_back(rows);
-  void* slot = nullptr;
-  HIPCHK(hipMalloc(&slot, ((size_t)total + 1) * IDX_SLOT_BYTES));
-  E->graph_allocs.push_back(slot);
+  tmp_b.reset();
+  DevBuf<uint4> slot_b;
+  TRY(slot_b.ensure_exact((size_t)total + 1, err));
+  uint4* const slot = slot_b.p;
   HIPCHK(hipMemsetAsync(slot, 0xFF, ((size_t)total + 1) * IDX_SLOT_BYTES, s));
-  launch_index_build(E->g, E->dp.turn_units, index_cost_bound(*r), row_cnt, rows, (uint4*)slot, true, s);
+  launch_index_build(E->g, E->dp.turn_units, index_cost_bound(*r), row_cnt, rows, slot, true, s);
   HIPCHK(hipGetLastError());
-  SrcRec* src = nullptr;
-  HIPCHK(hipMalloc(&src, ((size_t)E->g.n_edges + 1) * sizeof(SrcRec)));
-  E->graph_allocs.push_back(src);
+  DevBuf<SrcRec> src_b;
+  TRY(src_b.ensure_exact((size_t)E->g.n_edges + 1, err));
+  SrcRec* const src = src_b.p;
   launch_src_pack(E->g, rows, src, s);
   HIPCHK(hipGetLastError());
   std::vector<int32_t> cnt((size_t)N);
   HIPCHK(hipMemcpyAsync(cnt.data(), row_cnt, (size_t)N * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  E->graph_allocs.push_back(rows_b.release());
+  E->graph_allocs.push_back(slot_b.release());
+  E->graph_allocs.push_back(src_b.release());
   for (int32_t c : cnt) {
     out.incomplete += c < 0;
     out.entries += c > 0 ? c : 0;
@@ -566,7 +484,7 @@ int build_index_at(otm_engine* E, float* r, bool shrink, size_t budget, IndexBui
   out.X.row = rows;
   out.X.src = src;
   out.src_bytes = (int64_t)E->g.n_edges * (int64_t)sizeof(SrcRec);
-  out.X.slot = (const uint4*)slot;
+  out.X.slot = slot;
   out.X.load_pct = pct;
   return OTM_OK;
 }
@@ -597,8 +515,7 @@ int build_index(otm_engine* E, std::string* err) {
   // this radius exceed it gets a smaller radius; below 100 m the index is left
   // off and the online tiers answer everything (same results, slower).
   IndexBuilt full;
-  int rc = build_index_at(E, &E->index_rmax, true, index_budget(), full, err);
-  if (rc != OTM_OK) return rc;
+  TRY(build_index_at(E, &E->index_rmax, true, index_budget(), full, err));
   E->idx = full.X;
   E->index_entries = full.entries;
   E->index_slots = full.slots;
@@ -621,8 +538,7 @@ int build_index(otm_engine* E, std::string* err) {
   for (float rn : radii) {
     if (nl == NEAR_LEVELS || !(E->idx.rmax > 0.0f) || rn < 100.0f || rn >= E->idx.rmax) continue;
     IndexBuilt near;
-    rc = build_index_at(E, &rn, false, index_budget(), near, err);
-    if (rc != OTM_OK) return rc;
+    TRY(build_index_at(E, &rn, false, index_budget(), near, err));
     if (rn > 0.0f) {
       E->index_near_level_entries[nl] = near.entries;
       E->index_near_slots += near.slots;
@@ -638,60 +554,28 @@ int build_index(otm_engine* E, std::string* err) {
   return OTM_OK;
 }
 
+// What is not a buffer: the graph's arrays, the windows, streams and events
+// (the buffers go with the engine, ~otm_engine).  Safe on a half-built engine
+// and twice.
 void engine_free(otm_engine* E) {
   if (E->device >= 0) (void)hipSetDevice(E->device);
   for (void* p : E->graph_allocs) (void)hipFree(p);
   E->graph_allocs.clear();
-  otm_engine::Buf* bufs[] = {
-      &E->in_off,        &E->in_lat,       &E->in_lon,         &E->in_time,        &E->in_acc,     &E->in_blob,
-      &E->pt_trace,
-      &E->is_col,        &E->prevc,        &E->nextc,        &E->gc,             &E->ncand,          &E->cand_eo,      &E->cand_em,
-      &E->cand_xeo,      &E->cand_xem,
-      &E->probe,         &E->col_prev,     &E->kq_prev,        &E->vmeta,  &E->colrec, &E->colrec_pos,        &E->trans_off,      &E->trans,          &E->bp,         &E->state,      &E->chosen,
-      &E->chain_start,   &E->route_dist,   &E->ipos,   &E->path_off,       &E->path_len,       &E->path_pool,  &E->trace_err,
-      &E->spill_list1, &E->spill_list2, &E->counters_i32, &E->scan_tmp, &E->snap,   &E->big_key,
-      &E->big_lab,       &E->big_inq,      &E->big_fr,         &E->big_ins,        &E->big_prev,
-      &E->huge_key,      &E->huge_lab,     &E->huge_inq,       &E->huge_fr,        &E->huge_ins,         &E->huge_prev,
-      &E->cbig_key,      &E->cbig_val,     &E->cbig_skey,
-      &E->spill_list3, &E->o_traces,       &E->o_seg_cnt,  &E->o_way_cnt,
-      &E->o_segments,    &E->o_seg_gidx,   &E->o_way_ids,      &E->o_reports,  &E->o_rep_cnt,  &E->seg_ub,
-      &E->f_seg_off,     &E->f_way_off,    &E->f_rep_off,      &E->f_segs,     &E->f_ways,     &E->f_reps,
-      &E->f_traces,
-      &E->abort_flag,    &E->pts,          &E->rs_blob,      &E->ord_tile,      &E->ord_cnt,      &E->ord_cursor,     &E->ord_grp,    &E->ord_item,
-      &E->d_req,         &E->req_cnt,      &E->req_ok,     &E->req_lat,    &E->req_lon,    &E->req_time,   &E->req_acc,
-      &E->resp_hdr,      &E->resp_seg,     &E->resp_rep,       &E->resp_hlen,      &E->resp_slen,  &E->resp_rlen,
-      &E->resp_blen,     &E->resp_host,    &E->resp_blob,
-      &E->flush_slots,   &E->flush_len,    &E->flush_blob,     &E->flush_meta,     &E->win_peer_counts,
-      &E->win_peer_sums, &E->pairs_ckey,   &E->pairs_skey,     &E->pairs_cidx,     &E->pairs_sidx,
-      &E->pairs_sort_tmp, &E->pairs_meta,  &E->pairs_in,       &E->pm_key,         &E->pm_val,     &E->pm_ctr,
-      &E->pp_key,        &E->pp_val};
   pairs_drop(E);
   if (E->win_counts) (void)hipFree(E->win_counts);
   if (E->win_sums) (void)hipFree(E->win_sums);
   E->win_counts = E->win_sums = nullptr;
   E->win_open = false;
-  for (auto* b : bufs) {
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
-  for (auto* b : {&E->h_traces, &E->h_segs, &E->h_reps_dense, &E->h_ways, &E->h_tot, &E->h_in, &E->h_status, &E->h_pts,
-                  &E->h_req, &E->h_req_ok, &E->h_resp, &E->h_resp_meta, &E->h_flush, &E->h_flush_meta}) {
-    if (b->p) (void)hipHostFree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
   if (E->sync_ev) (void)hipEventDestroy(E->sync_ev);
   E->sync_ev = nullptr;
   for (hipEvent_t ev : E->req_ev) (void)hipEventDestroy(ev);
   E->req_ev.clear();
   if (E->req_copy) (void)hipStreamDestroy(E->req_copy);
   E->req_copy = nullptr;
-  if (E->ctr) (void)hipFree(E->ctr);
-  if (E->ctr_save) (void)hipFree(E->ctr_save);
-  E->ctr = E->ctr_save = nullptr;
-  for (auto& e : E->kev)
+  for (auto& e : E->kev) {
     if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
   if (E->stream) (void)hipStreamDestroy(E->stream);
   E->stream = nullptr;
 }
@@ -703,109 +587,106 @@ static int max_log2(const char* env, int dflt) {
   return v ? std::min(dflt, std::atoi(v)) : dflt;
 }
 
+// ---- One batch's device arrays.  Each step below sizes its arrays and binds
+// them to the kernels' argument structs, one line an array: its field, its
+// buffer, its element count.
+
 // The candidate HBM tier's tables (kernels.h CAND_BIG_SLOTS): none until a
 // probe outgrows the LDS tier; k_candidates<true> clears them per probe.
-static int ensure_cand(otm_engine* E, std::string* err) {
-  if (E->cand_log2 <= 0) return OTM_OK;
-  const size_t n = (size_t)CAND_BIG_SLOTS << E->cand_log2;
-  int rc;
-  if ((rc = ensure_grow(E->cbig_key, n * 4, err))) return rc;
-  if ((rc = ensure_grow(E->cbig_val, n * 8, err))) return rc;
-  if ((rc = ensure_grow(E->cbig_skey, n / 2 * 8, err))) return rc;
+static int ensure_cand(otm_engine* E, DevWork& w, std::string* err) {
+  const size_t n = E->cand_log2 > 0 ? (size_t)CAND_BIG_SLOTS << E->cand_log2 : 0;
+  w.cand_final = E->cand_final;
+  w.cand_log2 = E->cand_log2;
+  TRY(bind_grow(w.cbig_key, E->cbig_key, n, err));
+  TRY(bind_grow(w.cbig_val, E->cbig_val, n, err));
+  TRY(bind_grow(w.cbig_skey, E->cbig_skey, n / 2, err));
   return OTM_OK;
 }
 
 // The huge search tier's tables (kernels.h HUGE_SLOTS): none until a search
 // outgrows the global tier; then 2^huge_log2 slots each, grown 4x and the batch
 // redone whenever a search does not fit (engine_match).
-static int ensure_huge(otm_engine* E, std::string* err) {
-  if (E->huge_log2 <= 0) return OTM_OK;
-  const size_t n = (size_t)HUGE_SLOTS << E->huge_log2;
-  int rc;
-  if ((rc = ensure_grow(E->huge_key, n * 4, err))) return rc;
-  if ((rc = ensure_grow(E->huge_lab, n * 8, err))) return rc;
-  if ((rc = ensure_grow(E->huge_inq, n * 4, err))) return rc;
-  if ((rc = ensure_grow(E->huge_fr, n * 8, err))) return rc;
-  if ((rc = ensure_grow(E->huge_ins, (size_t)HUGE_SLOTS * huge_limit(E->huge_log2) * 4, err))) return rc;
-  if ((rc = ensure_grow(E->huge_prev, (size_t)HUGE_SLOTS * 4, err))) return rc;
-  if (E->huge_ready_log2 != E->huge_log2) {
+static int ensure_huge(otm_engine* E, DevWork& w, std::string* err) {
+  const size_t n = E->huge_log2 > 0 ? (size_t)HUGE_SLOTS << E->huge_log2 : 0;
+  w.huge_log2 = E->huge_log2;
+  w.huge_final = E->huge_final;
+  TRY(bind_grow(w.huge_key, E->huge_key, n, err));
+  TRY(bind_grow(w.huge_lab, E->huge_lab, n, err));
+  TRY(bind_grow(w.huge_inq, E->huge_inq, n, err));
+  TRY(bind_grow(w.huge_fr, E->huge_fr, n * 2, err));  // two frontier arrays a table
+  TRY(bind_grow(w.huge_ins, E->huge_ins, n ? (size_t)HUGE_SLOTS * huge_limit(E->huge_log2) : 0, err));
+  TRY(bind_grow(w.huge_prev, E->huge_prev, n ? (size_t)HUGE_SLOTS : 0, err));
+  if (n && E->huge_ready_log2 != E->huge_log2) {
     // (re)sized tables start clean, their "last inserted" lists marking the
     // whole table for the first search (-1)
     E->huge_ready_log2 = E->huge_log2;
-    HIPCHK(hipMemsetAsync(E->huge_key.p, 0xFF, n * 4, E->stream));
-    HIPCHK(hipMemsetAsync(E->huge_lab.p, 0xFF, n * 8, E->stream));
-    HIPCHK(hipMemsetAsync(E->huge_inq.p, 0, n * 4, E->stream));
-    HIPCHK(hipMemsetAsync(E->huge_prev.p, 0xFF, (size_t)HUGE_SLOTS * 4, E->stream));
+    HIPCHK(hipMemsetAsync(w.huge_key, 0xFF, n * sizeof *w.huge_key, E->stream));
+    HIPCHK(hipMemsetAsync(w.huge_lab, 0xFF, n * sizeof *w.huge_lab, E->stream));
+    HIPCHK(hipMemsetAsync(w.huge_inq, 0, n * sizeof *w.huge_inq, E->stream));
+    HIPCHK(hipMemsetAsync(w.huge_prev, 0xFF, (size_t)HUGE_SLOTS * sizeof *w.huge_prev, E->stream));
   }
   return OTM_OK;
 }
 
-static int ensure_big(otm_engine* E, std::string* err) {
+// The global search tier's tables: one size for the engine's life.
+static int ensure_big(otm_engine* E, DevWork& w, std::string* err) {
   const size_t n = (size_t)BIG_SLOTS * BIG_TABLE_CAP;
-  int rc;
-  const void* before = E->big_prev.p;
-  if ((rc = ensure(E->big_key, n * 4, err))) return rc;
-  if ((rc = ensure(E->big_lab, n * 8, err))) return rc;
-  if ((rc = ensure(E->big_inq, n * 4, err))) return rc;
-  if ((rc = ensure(E->big_fr, n * 8, err))) return rc;
-  if ((rc = ensure(E->big_ins, (size_t)BIG_SLOTS * SEARCH_LIMIT * 4, err))) return rc;
-  if ((rc = ensure(E->big_prev, (size_t)BIG_SLOTS * 4, err))) return rc;
-  if (E->big_prev.p != before) {
+  bool fresh;
+  TRY(bind_buf(w.big_key, E->big_key, n, err));
+  TRY(bind_buf(w.big_lab, E->big_lab, n, err));
+  TRY(bind_buf(w.big_inq, E->big_inq, n, err));
+  TRY(bind_buf(w.big_fr, E->big_fr, n * 2, err));  // two frontier arrays a table
+  TRY(bind_buf(w.big_ins, E->big_ins, (size_t)BIG_SLOTS * SEARCH_LIMIT, err));
+  TRY(bind_buf(w.big_prev, E->big_prev, (size_t)BIG_SLOTS, err, &fresh));
+  if (fresh) {
     // fresh tables start clean (each search then clears only what the last
     // one inserted: kernels.hip ta_search)
-    HIPCHK(hipMemsetAsync(E->big_key.p, 0xFF, n * 4, E->stream));
-    HIPCHK(hipMemsetAsync(E->big_lab.p, 0xFF, n * 8, E->stream));
-    HIPCHK(hipMemsetAsync(E->big_inq.p, 0, n * 4, E->stream));
-    HIPCHK(hipMemsetAsync(E->big_prev.p, 0, (size_t)BIG_SLOTS * 4, E->stream));
+    HIPCHK(hipMemsetAsync(w.big_key, 0xFF, n * sizeof *w.big_key, E->stream));
+    HIPCHK(hipMemsetAsync(w.big_lab, 0xFF, n * sizeof *w.big_lab, E->stream));
+    HIPCHK(hipMemsetAsync(w.big_inq, 0, n * sizeof *w.big_inq, E->stream));
+    HIPCHK(hipMemsetAsync(w.big_prev, 0, (size_t)BIG_SLOTS * sizeof *w.big_prev, E->stream));
   }
   return OTM_OK;
 }
 
-// One attempt at a batch, enqueued with no host synchronisation: buffers are
-// sized from capacities (transition matrices, path pool) that the kernels
-// check; an overflow sets w.abort, every later kernel returns at once, and
-// engine_match grows the capacity and runs the batch again -- whole
-// (from = RESUME_ALL), or from the on-demand tier that overflowed (Resume).
-static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* err,
-                             int from = RESUME_ALL) {
-  const int64_t NP = b.n_points;
-  const int32_t NT = b.n_traces;
+// The per-point and per-trace work arrays, the path pool and the scans' scratch.
+static int bind_point_work(otm_engine* E, int64_t NP, int32_t NT, DevWork& w, std::string* err) {
   const size_t Pn = (size_t)NP + 1;
-  int rc;
-#define ENS(buf, bytes) \
-  if ((rc = ensure(E->buf, (bytes), err))) return rc;
-  ENS(pt_trace, Pn * 4);
-  ENS(is_col, Pn);
-  ENS(prevc, Pn * 4);
-  ENS(nextc, Pn * 4);
-  ENS(gc, Pn * 4);
-  ENS(ncand, Pn * 4);
-  ENS(cand_eo, Pn * KIN * 8);  // inline candidate slots {edge, offset bits}
-  ENS(cand_em, Pn * KIN * 4);  //   ... and their emissions
-  ENS(cand_xeo, Pn * KX * 8);  // slots KIN.. (only the wider points touch them)
-  ENS(cand_xem, Pn * KX * 4);
-  ENS(probe, Pn * 16);
-  ENS(col_prev, Pn * 4);
-  ENS(kq_prev, Pn * 4);
-  ENS(vmeta, Pn);
-  ENS(colrec, Pn * 16);
-  ENS(colrec_pos, Pn * 4);
-  ENS(trans_off, Pn * 8);
-  ENS(bp, Pn * KMAX);
-  ENS(state, Pn * 4);
-  ENS(chosen, Pn * 8);
-  ENS(chain_start, Pn);
-  ENS(route_dist, Pn * 4);
-  ENS(ipos, Pn * 4);
-  ENS(path_off, Pn * 4);
-  ENS(path_len, Pn * 4);
-  ENS(trace_err, ((size_t)NT + 1) * 4);
-  ENS(spill_list1, Pn * 4);
-  ENS(spill_list2, Pn * 4);
-  ENS(spill_list3, Pn * 4);
-  ENS(counters_i32, CTR_WORDS * 4);  // (kernels.h CtrSlot)
-  ENS(snap, sizeof(SnapBuf));
-  ENS(abort_flag, 16);
+  TRY(bind_buf(w.pt_trace, E->pt_trace, Pn, err));
+  TRY(bind_buf(w.is_col, E->is_col, Pn, err));
+  TRY(bind_buf(w.prevc, E->prevc, Pn, err));
+  TRY(bind_buf(w.nextc, E->nextc, Pn, err));
+  TRY(bind_buf(w.gc, E->gc, Pn, err));
+  TRY(bind_buf(w.ncand, E->ncand, Pn, err));
+  TRY(bind_buf(w.cand_eo, E->cand_eo, Pn * KIN, err));  // inline candidate slots {edge, offset bits}
+  TRY(bind_buf(w.cand_em, E->cand_em, Pn * KIN, err));  //   ... and their emissions
+  TRY(bind_buf(w.cand_xeo, E->cand_xeo, Pn * KX, err));  // slots KIN.. (only the wider points touch them)
+  TRY(bind_buf(w.cand_xem, E->cand_xem, Pn * KX, err));
+  TRY(bind_buf(w.probe, E->probe, Pn, err));
+  TRY(bind_buf(w.col_prev, E->col_prev, Pn, err));
+  TRY(bind_buf(w.kq_prev, E->kq_prev, Pn, err));
+  TRY(bind_buf(w.vmeta, E->vmeta, Pn, err));
+  // ordered column records for K4 (spatial-order batches; the others read
+  // the per-point arrays)
+  TRY(bind_buf(w.colrec, E->colrec, Pn, err));
+  TRY(bind_buf(w.colrec_pos, E->colrec_pos, Pn, err));
+  TRY(bind_buf(w.trans_off, E->trans_off, Pn, err));
+  TRY(bind_buf(w.bp, E->bp, Pn * KMAX, err));
+  TRY(bind_buf(w.state, E->state, Pn, err));
+  TRY(bind_buf(w.chosen, E->chosen, Pn, err));
+  TRY(bind_buf(w.chain_start, E->chain_start, Pn, err));
+  TRY(bind_buf(w.route_dist, E->route_dist, Pn, err));
+  TRY(bind_buf(w.ipos, E->ipos, Pn, err));
+  TRY(bind_buf(w.path_off, E->path_off, Pn, err));
+  TRY(bind_buf(w.path_len, E->path_len, Pn, err));
+  TRY(bind_buf(w.trace_err, E->trace_err, (size_t)NT + 1, err));
+  TRY(bind_buf(w.spill_list1, E->spill_list1, Pn, err));
+  TRY(bind_buf(w.spill_list2, E->spill_list2, Pn, err));
+  TRY(bind_buf(w.spill_list3, E->spill_list3, Pn, err));
+  TRY(bind_buf(w.counters_i32, E->counters_i32, CTR_WORDS, err));  // (kernels.h CtrSlot)
+  TRY(E->snap.ensure(1, err));
+  w.snap = &E->snap.p->stage[0][0];
+  TRY(bind_buf(w.abort, E->abort_flag, 4, err));
   // Capacities of the transition matrices and the path pool: sized from the
   // batch (kept at the largest seen), so the abort -> regrow -> redo loop of
   // engine_match is the exception.  OTM_TRANS_CAP / OTM_POOL_CAP pin the
@@ -819,11 +700,72 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     E->trans_cap = std::max<int64_t>(E->trans_cap, (int64_t)Pn * 48 + 4096);
     E->pool_cap = std::max<int32_t>(E->pool_cap, (int32_t)std::min<size_t>(Pn * 8, (size_t)1 << 30));
   }
-  ENS(o_traces, ((size_t)NT + 1) * sizeof(otm_trace_result));
-  ENS(o_seg_cnt, ((size_t)NT + 1) * 4);
-  ENS(o_way_cnt, ((size_t)NT + 1) * 4);
-  ENS(scan_tmp, scan_tmp_bytes(NP > NT ? NP : NT) + 256);
-  ENS(path_pool, (size_t)E->pool_cap * 4);
+  TRY(E->scan_tmp.ensure(scan_tmp_bytes(NP > NT ? NP : NT) + 256, err));
+  TRY(bind_buf(w.path_pool, E->path_pool, (size_t)E->pool_cap, err));
+  w.pool_cap = E->pool_cap;
+  w.idx = E->idx;
+  for (int l = 0; l < NEAR_LEVELS; ++l) w.idxn[l] = E->idxn[l];
+  return OTM_OK;
+}
+
+// The spatial work order's arrays (tile_cnt null: no order this batch).
+static int bind_order(otm_engine* E, int64_t NP, bool ordered, DevOrder& ord, std::string* err) {
+  const size_t Pn = (size_t)NP + 1;
+  TRY(bind_buf(ord.tile, E->ord_tile, Pn, err));
+  TRY(bind_buf(ord.tile_cnt, E->ord_cnt, ORDER_TILES, err));
+  TRY(bind_buf(ord.cursor, E->ord_cursor, ORDER_TILES, err));
+  TRY(bind_buf(ord.grp, E->ord_grp, ORDER_GROUPS + 1, err));
+  TRY(bind_buf(ord.item, E->ord_item, Pn, err));
+  if (!ordered) ord.tile_cnt = nullptr;
+  return OTM_OK;
+}
+
+// The transition matrices.  k_viterbi_row prefetches whole windows: past a
+// chunk's blocks it reads whatever the allocation holds there (never past
+// trans_cap), and that must never be a NaN.  So a new allocation starts as
+// zeros; from then on it holds only costs, this batch's or an earlier one's.
+static int bind_trans(otm_engine* E, DevWork& w, hipStream_t s, std::string* err) {
+  bool fresh;
+  TRY(bind_buf(w.trans, E->trans, (size_t)E->trans_cap + 1, err, &fresh));
+  if (fresh) HIPCHK(hipMemsetAsync(E->trans.p, 0, E->trans.bytes(), s));
+  w.trans_cap = E->trans_cap;
+  return OTM_OK;
+}
+
+// Segments, way ids and reports are written in ONE walk per trace, each trace
+// into a region sized by an upper bound (DevOut): every matched point adds
+// <= 2 + its path length, and the path lengths sum to at most the pool.
+static size_t out_region_cap(const otm_engine* E, int64_t NP) { return 2 * (size_t)NP + (size_t)E->pool_cap + 1; }
+
+// A batch's outputs, for the batch (engine_match_once) and for its fetch
+// (fetch_compact, with the same counts: nothing is sized again).
+static int bind_out(otm_engine* E, int32_t NT, int64_t NP, DevOut& o, std::string* err) {
+  const size_t Tn = (size_t)NT + 1, cap = out_region_cap(E, NP);
+  TRY(bind_buf(o.traces, E->o_traces, Tn, err));
+  TRY(bind_buf(o.seg_cnt, E->o_seg_cnt, Tn, err));
+  TRY(bind_buf(o.way_cnt, E->o_way_cnt, Tn, err));
+  TRY(bind_buf(o.seg_base, E->seg_ub, Tn, err));
+  TRY(bind_buf(o.segments, E->o_segments, cap, err));
+  TRY(bind_buf(o.seg_gidx, E->o_seg_gidx, cap, err));
+  TRY(bind_buf(o.reports, E->o_reports, cap, err));
+  TRY(bind_buf(o.way_ids, E->o_way_ids, cap, err));
+  TRY(bind_buf(o.rep_cnt, E->o_rep_cnt, Tn, err));
+  return OTM_OK;
+}
+
+// One attempt at a batch, enqueued with no host synchronisation: buffers are
+// sized from capacities (transition matrices, path pool) that the kernels
+// check; an overflow sets w.abort, every later kernel returns at once, and
+// engine_match grows the capacity and runs the batch again -- whole
+// (from = RESUME_ALL), or from the on-demand tier that overflowed (Resume).
+// Each stage's arrays are bound just before its launches, so an allocation
+// (which waits for the device) comes where it always came.
+static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* err,
+                             int from = RESUME_ALL) {
+  const int64_t NP = b.n_points;
+  const int32_t NT = b.n_traces;
+  DevWork w{};
+  TRY(bind_point_work(E, NP, NT, w, err));
 
   // Small batches (the batcher's rounds) are latency bound: too few probes
   // to hide a lane's serial cell walk, and the spatial order's fixed cost
@@ -833,64 +775,13 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     dp.order_mask = 0;
     dp.cand_wave_all = 1;
   }
-
-  DevWork w{};
-  w.pt_trace = P<int32_t>(E->pt_trace);
-  w.is_col = P<uint8_t>(E->is_col);
-  w.prevc = P<int32_t>(E->prevc);
-  w.nextc = P<int32_t>(E->nextc);
-  w.gc = P<float>(E->gc);
-  w.ncand = P<int32_t>(E->ncand);
-  w.probe = P<float4>(E->probe);
-  w.cand_eo = P<int2>(E->cand_eo);
-  w.cand_em = P<float>(E->cand_em);
-  w.cand_xeo = P<int2>(E->cand_xeo);
-  w.cand_xem = P<float>(E->cand_xem);
-  w.col_prev = P<int32_t>(E->col_prev);
-  w.kq_prev = P<int32_t>(E->kq_prev);
-  w.vmeta = P<uint8_t>(E->vmeta);
-  {
-    // ordered column records for K4 (spatial-order batches; the others read
-    // the per-point arrays)
-    w.colrec = P<int4>(E->colrec);
-    w.colrec_pos = P<int32_t>(E->colrec_pos);
-  }
-  w.trans_off = P<int64_t>(E->trans_off);
-  w.bp = P<uint8_t>(E->bp);
-  w.state = P<int32_t>(E->state);
-  w.chosen = P<int2>(E->chosen);
-  w.chain_start = P<uint8_t>(E->chain_start);
-  w.route_dist = P<float>(E->route_dist);
-  w.ipos = P<float>(E->ipos);
-  w.path_off = P<int32_t>(E->path_off);
-  w.path_len = P<int32_t>(E->path_len);
-  w.path_pool = P<int32_t>(E->path_pool);
-  w.pool_cap = E->pool_cap;
-  w.trace_err = P<int32_t>(E->trace_err);
-  w.spill_list1 = P<int32_t>(E->spill_list1);
-  w.spill_list2 = P<int32_t>(E->spill_list2);
-  w.spill_list3 = P<int32_t>(E->spill_list3);
-  w.idx = E->idx;
-  for (int l = 0; l < NEAR_LEVELS; ++l) w.idxn[l] = E->idxn[l];
-  w.counters_i32 = P<int32_t>(E->counters_i32);
-  w.snap = &P<SnapBuf>(E->snap)->stage[0][0];
-  w.ctr = E->counting ? E->ctr : nullptr;
-  if (E->counting && from == RESUME_ALL) HIPCHK(hipMemsetAsync(E->ctr, 0, sizeof(DevCounters), s));
-  w.abort = P<int32_t>(E->abort_flag);
+  w.ctr = E->counting ? E->ctr.p : nullptr;
+  if (E->counting && from == RESUME_ALL) HIPCHK(hipMemsetAsync(E->ctr.p, 0, sizeof(DevCounters), s));
   // the counters' and abort flag's reset, the spill snapshots and the
   // transition capacity check ride in K1, K3, K4, K5 and K7 (kernels.h CtrSlot)
   Marks mk;
   mk.ev = E->timing ? E->kev : nullptr;
-  ENS(ord_tile, Pn * 2);
-  ENS(ord_cnt, ORDER_TILES * 4);
-  ENS(ord_cursor, ORDER_TILES * 4);
-  ENS(ord_grp, (ORDER_GROUPS + 1) * 4);
-  ENS(ord_item, Pn * 4);
-  w.ord.item = P<int32_t>(E->ord_item);
-  w.ord.grp = P<int32_t>(E->ord_grp);
-  w.ord.tile = P<uint16_t>(E->ord_tile);
-  w.ord.tile_cnt = dp.order_mask ? P<int32_t>(E->ord_cnt) : nullptr;
-  w.ord.cursor = P<int32_t>(E->ord_cursor);
+  TRY(bind_order(E, NP, dp.order_mask != 0, w.ord, err));
   if (from == RESUME_ALL) {
     launch_columns(E->g, b, dp, w, s, mk);
     if (dp.order_mask) {
@@ -900,48 +791,19 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
       mk.end(KN_ORDER, s);
     }
   }
-  if ((rc = ensure_cand(E, err))) return rc;
-  w.cand_final = E->cand_final;
-  w.cbig_key = P<uint32_t>(E->cbig_key);
-  w.cbig_val = P<unsigned long long>(E->cbig_val);
-  w.cbig_skey = P<unsigned long long>(E->cbig_skey);
-  w.cand_log2 = E->cand_log2;
+  TRY(ensure_cand(E, w, err));
   if (from <= RESUME_CAND_BIG) launch_candidates(E->g, b, dp, w, s, mk, from);
   // (k_links takes SNAP_AFTER_CAND: candidate probes the lane tier handed to
   // the wave tier; the counters start over for the transition tiers)
   if (from <= RESUME_CAND_BIG) {
     launch_links(b, dp, w, s, mk);
     mk.begin(KN_SCAN_TRANS, s);
-    scan_i64(w.trans_off, NP, E->scan_tmp.p, E->scan_tmp.cap, s);
+    scan_i64(w.trans_off, NP, E->scan_tmp.p, E->scan_tmp.cap(), s);
     mk.end(KN_SCAN_TRANS, s);
   }
-  {
-    // k_viterbi_row prefetches whole windows: past a chunk's blocks it reads
-    // whatever the allocation holds there (never past trans_cap), and that
-    // must never be a NaN.  So a new allocation starts as zeros; from then on
-    // it holds only costs, this batch's or an earlier one's.
-    const size_t cap0 = E->trans.cap;
-    ENS(trans, ((size_t)E->trans_cap + 1) * 4);
-    if (E->trans.cap != cap0) HIPCHK(hipMemsetAsync(E->trans.p, 0, E->trans.cap, s));
-  }
-  w.trans = P<float>(E->trans);
-  w.trans_cap = E->trans_cap;
-  if ((rc = ensure_big(E, err))) return rc;
-  w.big_key = P<uint32_t>(E->big_key);
-  w.big_lab = P<unsigned long long>(E->big_lab);
-  w.big_inq = P<uint32_t>(E->big_inq);
-  w.big_fr = P<uint32_t>(E->big_fr);
-  w.big_ins = P<uint32_t>(E->big_ins);
-  w.big_prev = P<int32_t>(E->big_prev);
-  if ((rc = ensure_huge(E, err))) return rc;
-  w.huge_key = P<uint32_t>(E->huge_key);
-  w.huge_lab = P<unsigned long long>(E->huge_lab);
-  w.huge_inq = P<uint32_t>(E->huge_inq);
-  w.huge_fr = P<uint32_t>(E->huge_fr);
-  w.huge_ins = P<uint32_t>(E->huge_ins);
-  w.huge_prev = P<int32_t>(E->huge_prev);
-  w.huge_log2 = E->huge_log2;
-  w.huge_final = E->huge_final;
+  TRY(bind_trans(E, w, s, err));
+  TRY(ensure_big(E, w, err));
+  TRY(ensure_huge(E, w, err));
   if (from <= RESUME_TRANS_HUGE) launch_transitions(E->g, b, dp, w, s, mk, E->trans_lanes, from);
   // (the first Viterbi launch takes SNAP_AFTER_TRANS: columns per transition
   // tier; the per-stage counters start over for the route tiers)
@@ -949,30 +811,12 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   launch_route(E->g, b, dp, w, s, mk, from);
   // (k_seg_bound takes SNAP_AFTER_ROUTE: steps per route tier)
 
-  // Segments, way ids and reports in ONE walk per trace, each trace writing
-  // into a region sized by an upper bound (DevOut): every matched point adds
-  // <= 2 + its path length, and the path lengths sum to at most the pool.
-  const size_t cap = 2 * (size_t)NP + (size_t)E->pool_cap + 1;
-  if (cap >= (size_t)INT32_MAX) {
+  if (out_region_cap(E, NP) >= (size_t)INT32_MAX) {
     *err = "batch too large for one launch (segment regions exceed 2^31)";
     return OTM_EINVAL;
   }
-  ENS(seg_ub, ((size_t)NT + 1) * 8);
-  ENS(o_segments, cap * sizeof(otm_segment));
-  ENS(o_seg_gidx, cap * 4);
-  ENS(o_reports, cap * sizeof(otm_report_rec));
-  ENS(o_way_ids, cap * 8);
-  ENS(o_rep_cnt, ((size_t)NT + 1) * 4);
   DevOut o{};
-  o.traces = E->o_traces.p;
-  o.seg_cnt = P<int32_t>(E->o_seg_cnt);
-  o.way_cnt = P<int32_t>(E->o_way_cnt);
-  o.rep_cnt = P<int32_t>(E->o_rep_cnt);
-  o.seg_base = P<int64_t>(E->seg_ub);
-  o.segments = E->o_segments.p;
-  o.seg_gidx = P<int32_t>(E->o_seg_gidx);
-  o.reports = E->o_reports.p;
-  o.way_ids = P<int64_t>(E->o_way_ids);
+  TRY(bind_out(E, NT, NP, o, err));
   {
     // the histogram binding lives on the parent; a clone reads it here
     otm_engine* H = E->parent ? const_cast<otm_engine*>(E->parent) : E;
@@ -983,10 +827,10 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     o.bin_kph = H->bin_kph;
     o.pairs = H->pairs_tab;  // (key null: no pair window)
   }
-  HIPCHK(hipMemsetAsync(E->seg_ub.p, 0, ((size_t)NT + 1) * 8, s));
-  launch_seg_bound(E->g, b, dp, w, P<int64_t>(E->seg_ub), s, mk);
+  HIPCHK(hipMemsetAsync(o.seg_base, 0, ((size_t)NT + 1) * sizeof *o.seg_base, s));
+  launch_seg_bound(E->g, b, dp, w, o.seg_base, s, mk);
   mk.begin(KN_SEG_SCAN, s);
-  scan_i64(P<int64_t>(E->seg_ub), NT, E->scan_tmp.p, E->scan_tmp.cap, s);
+  scan_i64(o.seg_base, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
   mk.end(KN_SEG_SCAN, s);
   launch_segments(E->g, b, w, o, s, mk);
   // K7b (DESIGN.md §3 rule 7b): only with a queue threshold; outside the timing marks
@@ -995,8 +839,8 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   // Every attempt writes the whole array, so a redone or resumed batch leaves one run's records.
   E->pts_n = -1;
   if (E->points_on) {
-    ENS(pts, Pn * sizeof(otm_matched_point));
-    launch_points(E->g, b, dp, w, P<otm_matched_point>(E->pts), s);
+    TRY(E->pts.ensure((size_t)NP + 1, err));
+    launch_points(E->g, b, dp, w, E->pts.p, s);
     E->pts_n = NP;
   }
   launch_report(b, E->drc, w, o, s, mk);
@@ -1005,14 +849,12 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   E->last_P = NP;
   E->last_S = -1;  // known after compaction (engine_fetch)
   E->last_W = -1;
-#undef ENS
   return OTM_OK;
 }
 
 int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* err) {
   if (!s) s = E->stream;
   const int64_t NP = b.n_points;
-  int rc;
   // A tier that ran out of HBM fails its overflowing traces for this batch
   // only: the next batch tries to grow it again (the growth cap, by contrast,
   // is final).  The guard lifts the batch's flags on every way out.
@@ -1025,17 +867,18 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     }
   } oom{E};
   int from = RESUME_ALL;
+  DevWork grown{};  // (the tiers' tables as a growth below leaves them: the next attempt binds them again)
   E->last_resumes = 0;
   for (int attempt = 0;; ++attempt) {
-    if ((rc = engine_match_once(E, b, s, err, from))) return rc;
+    TRY(engine_match_once(E, b, s, err, from));
     // the one synchronisation of a batch: did every capacity hold?
     // (gathered on the device, one copy into pinned memory)
-    if ((rc = ensure_pinned(E->h_status, sizeof(BatchStatus), err))) return rc;
-    BatchStatus* dst = &P<SnapBuf>(E->snap)->status;
-    launch_status(P<int32_t>(E->abort_flag), P<int64_t>(E->trans_off) + NP, P<int32_t>(E->counters_i32), dst, s);
+    TRY(E->h_status.ensure(1, err));
+    BatchStatus* dst = &E->snap.p->status;
+    launch_status(E->abort_flag.p, E->trans_off.p + NP, E->counters_i32.p, dst, s);
     HIPCHK(hipMemcpyAsync(E->h_status.p, dst, sizeof(BatchStatus), hipMemcpyDeviceToHost, s));
     HIPCHK(wait_batch(E, s, NP));
-    const BatchStatus st = *(const BatchStatus*)E->h_status.p;
+    const BatchStatus st = *E->h_status.p;
     const int32_t ab = st.abort;
     const int64_t ttotal = st.ttotal;
     E->last_trans = ttotal;
@@ -1055,7 +898,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
         E->huge_final = 1;
       } else {
         E->huge_log2 = next;
-        if (ensure_huge(E, err) != OTM_OK) {
+        if (ensure_huge(E, grown, err) != OTM_OK) {
           E->huge_log2 = prev;
           E->huge_final = 1;
           oom.huge = true;
@@ -1074,7 +917,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
         E->cand_final = 1;
       } else {
         E->cand_log2 = next;
-        if (ensure_cand(E, err) != OTM_OK) {
+        if (ensure_cand(E, grown, err) != OTM_OK) {
           E->cand_log2 = prev;
           E->cand_final = 1;
           oom.cand = true;
@@ -1100,8 +943,8 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     if (from != RESUME_ALL) {
       const SnapId snap = from == RESUME_CAND_BIG ? SNAP_AFTER_CAND
                                                   : (from == RESUME_TRANS_HUGE ? SNAP_AFTER_TRANS : SNAP_AFTER_ROUTE);
-      int32_t* ctr = P<int32_t>(E->counters_i32);
-      HIPCHK(hipMemcpyAsync(ctr, P<SnapBuf>(E->snap)->stage[snap], CTR_STAGE_WORDS * sizeof(int32_t),
+      int32_t* ctr = E->counters_i32.p;
+      HIPCHK(hipMemcpyAsync(ctr, E->snap.p->stage[snap], CTR_STAGE_WORDS * sizeof(int32_t),
                             hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemsetAsync(ctr + CTR_GROW_HUGE, 0, 4, s));
       HIPCHK(hipMemsetAsync(ctr + CTR_GROW_CAND, 0, 4, s));
@@ -1126,7 +969,6 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       for (int q = first[k]; q <= last[k]; ++q) E->stage_ms[k] += E->kernel_ms[q];
     }
   }
-#undef ENS
   return OTM_OK;
 }
 
@@ -1141,41 +983,47 @@ static hipError_t big_copy(void* dst, const void* src, size_t n, hipMemcpyKind k
   return hipMemcpyAsync(dst, src, n, k, s);
 }
 
+// The offsets of a host batch (n_points 0: derived from trace_off).
+static int validate_offsets(int32_t NT, const int64_t* trace_off, int64_t n_points, std::string* err) {
+  const int64_t NP = trace_off[NT];
+  if (trace_off[0] != 0 || NP < 0 || (n_points && n_points != NP)) {
+    *err = "batch trace_off inconsistent with n_points";
+    return OTM_EINVAL;
+  }
+  for (int32_t t = 0; t < NT; ++t)
+    if (trace_off[t + 1] < trace_off[t]) {
+      *err = "batch trace_off not monotonic";
+      return OTM_EINVAL;
+    }
+  return OTM_OK;
+}
+
 int engine_match_host(otm_engine* E, const otm_batch* in, std::string* err) {
   const int32_t NT = in->n_traces;
   if (NT < 0 || !in->trace_off) {
     *err = "invalid batch";
     return OTM_EINVAL;
   }
+  TRY(validate_offsets(NT, in->trace_off, in->n_points, err));
   const int64_t NP = in->trace_off[NT];
-  if (in->trace_off[0] != 0 || NP < 0 || (in->n_points && in->n_points != NP)) {
-    *err = "batch trace_off inconsistent with n_points";
-    return OTM_EINVAL;
-  }
-  for (int32_t t = 0; t < NT; ++t)
-    if (in->trace_off[t + 1] < in->trace_off[t]) {
-      *err = "batch trace_off not monotonic";
-      return OTM_EINVAL;
-    }
-  int rc;
-  if ((rc = ensure(E->in_off, ((size_t)NT + 1) * 8, err))) return rc;
-  if ((rc = ensure(E->in_lat, (size_t)NP * 4, err))) return rc;
-  if ((rc = ensure(E->in_lon, (size_t)NP * 4, err))) return rc;
-  if ((rc = ensure(E->in_time, (size_t)NP * 8, err))) return rc;
-  if ((rc = ensure(E->in_acc, (size_t)NP * 4, err))) return rc;
-  hipStream_t s = E->stream;
-  const size_t b_off = ((size_t)NT + 1) * 8, b_pt = (size_t)NP * 4, b_tm = (size_t)NP * 8;
   DevBatch b;
   b.n_traces = NT;
   b.n_points = NP;
+  TRY(bind_buf(b.trace_off, E->in_off, (size_t)NT + 1, err));
+  TRY(bind_buf(b.lat, E->in_lat, (size_t)NP, err));
+  TRY(bind_buf(b.lon, E->in_lon, (size_t)NP, err));
+  TRY(bind_buf(b.time, E->in_time, (size_t)NP, err));
+  TRY(bind_buf(b.acc, E->in_acc, (size_t)NP, err));
+  hipStream_t s = E->stream;
+  const size_t b_off = ((size_t)NT + 1) * 8, b_pt = (size_t)NP * 4, b_tm = (size_t)NP * 8;
   if (NP <= (int64_t)1 << 18) {
     // small batches: one host copy into pinned staging, then ONE DMA into a
     // device blob laid out the same way (offsets, times, lat, lon, accuracy:
     // every section stays 8-byte aligned) -- the batcher's rounds, single requests
     const size_t total = b_off + b_tm + 3 * b_pt;
-    if ((rc = ensure_pinned(E->h_in, total, err))) return rc;
-    if ((rc = ensure(E->in_blob, total, err))) return rc;
-    char* h = (char*)E->h_in.p;
+    TRY(E->h_in.ensure(total, err));
+    TRY(E->in_blob.ensure(total, err));
+    char* h = E->h_in.p;
     std::memcpy(h, in->trace_off, b_off);
     if (NP) {
       std::memcpy(h + b_off, in->time, b_tm);
@@ -1184,7 +1032,7 @@ int engine_match_host(otm_engine* E, const otm_batch* in, std::string* err) {
       std::memcpy(h + b_off + b_tm + 2 * b_pt, in->accuracy, b_pt);
     }
     HIPCHK(hipMemcpyAsync(E->in_blob.p, h, total, hipMemcpyHostToDevice, s));
-    const char* d = (const char*)E->in_blob.p;
+    const char* d = E->in_blob.p;
     b.trace_off = (const int64_t*)d;
     b.time = (const double*)(d + b_off);
     b.lat = (const float*)(d + b_off + b_tm);
@@ -1198,11 +1046,6 @@ int engine_match_host(otm_engine* E, const otm_batch* in, std::string* err) {
   HIPCHK(big_copy(E->in_lon.p, in->lon, b_pt, h2d, s));
   HIPCHK(big_copy(E->in_time.p, in->time, b_tm, h2d, s));
   HIPCHK(big_copy(E->in_acc.p, in->accuracy, b_pt, h2d, s));
-  b.trace_off = (const int64_t*)E->in_off.p;
-  b.lat = (const float*)E->in_lat.p;
-  b.lon = (const float*)E->in_lon.p;
-  b.time = (const double*)E->in_time.p;
-  b.acc = (const float*)E->in_acc.p;
   return engine_match(E, b, s, err);
 }
 
@@ -1219,16 +1062,8 @@ int validate_compact(const otm_batch_compact* in, int64_t* np, std::string* err)
     *err = "invalid batch";
     return OTM_EINVAL;
   }
+  TRY(validate_offsets(NT, in->trace_off, in->n_points, err));
   const int64_t NP = in->trace_off[NT];
-  if (in->trace_off[0] != 0 || NP < 0 || (in->n_points && in->n_points != NP)) {
-    *err = "batch trace_off inconsistent with n_points";
-    return OTM_EINVAL;
-  }
-  for (int32_t t = 0; t < NT; ++t)
-    if (in->trace_off[t + 1] < in->trace_off[t]) {
-      *err = "batch trace_off not monotonic";
-      return OTM_EINVAL;
-    }
   if (NP > 0 && (!in->lat || !in->lon || !in->time_delta || !in->accuracy)) {
     *err = "invalid batch";
     return OTM_EINVAL;
@@ -1240,8 +1075,7 @@ int validate_compact(const otm_batch_compact* in, int64_t* np, std::string* err)
 int engine_match_compact(otm_engine* E, const otm_batch_compact* in, std::string* err) {
   const int32_t NT = in->n_traces;
   int64_t NP = 0;
-  int rc;
-  if ((rc = validate_compact(in, &NP, err))) return rc;
+  TRY(validate_compact(in, &NP, err));
   const size_t b_off = ((size_t)NT + 1) * 8, b_base = (size_t)NT * 8, b_pt = (size_t)NP * 4,
                b_acc = ((size_t)NP * 2 + 7) & ~(size_t)7;
   // device: [offsets | time bases | lat | lon | time deltas | accuracies], each
@@ -1251,15 +1085,18 @@ int engine_match_compact(otm_engine* E, const otm_batch_compact* in, std::string
   const size_t o_base = al(b_off), o_lat = al(o_base + b_base), o_lon = al(o_lat + b_pt), o_dt = al(o_lon + b_pt),
                o_acc = al(o_dt + b_pt);
   const size_t total = o_acc + b_acc;
-  if ((rc = ensure(E->in_blob, total, err))) return rc;
-  if ((rc = ensure(E->in_time, (size_t)NP * 8 + 8, err))) return rc;
-  if ((rc = ensure(E->in_acc, (size_t)NP * 4 + 8, err))) return rc;
+  DevBatch b;
+  b.n_traces = NT;
+  b.n_points = NP;
+  TRY(E->in_blob.ensure(total, err));
+  TRY(bind_buf(b.time, E->in_time, (size_t)NP + 1, err));
+  TRY(bind_buf(b.acc, E->in_acc, (size_t)NP + 2, err));
   hipStream_t s = E->stream;
-  char* d = (char*)E->in_blob.p;
+  char* d = E->in_blob.p;
   if (NP <= (int64_t)1 << 18) {
     // small batches: one host copy into pinned staging, then ONE DMA
-    if ((rc = ensure_pinned(E->h_in, total, err))) return rc;
-    char* h = (char*)E->h_in.p;
+    TRY(E->h_in.ensure(total, err));
+    char* h = E->h_in.p;
     std::memcpy(h, in->trace_off, b_off);
     if (NT) std::memcpy(h + o_base, in->time_base, b_base);
     if (NP) {
@@ -1279,15 +1116,10 @@ int engine_match_compact(otm_engine* E, const otm_batch_compact* in, std::string
     HIPCHK(big_copy(d + o_acc, in->accuracy, (size_t)NP * 2, h2d, s));
   }
   launch_expand_compact((const int64_t*)d, (const int64_t*)(d + o_base), (const int32_t*)(d + o_dt),
-                        (const int16_t*)(d + o_acc), (double*)E->in_time.p, (float*)E->in_acc.p, NT, s);
-  DevBatch b;
-  b.n_traces = NT;
-  b.n_points = NP;
+                        (const int16_t*)(d + o_acc), E->in_time.p, E->in_acc.p, NT, s);
   b.trace_off = (const int64_t*)d;
   b.lat = (const float*)(d + o_lat);
   b.lon = (const float*)(d + o_lon);
-  b.time = (const double*)E->in_time.p;
-  b.acc = (const float*)E->in_acc.p;
   return engine_match(E, b, s, err);
 }
 
@@ -1300,31 +1132,30 @@ static size_t req_blob_bytes(int32_t n, size_t bytes) { return req_hdr_bytes(n) 
 
 int engine_stage_requests(otm_engine* E, int32_t n, size_t bytes, bool bodies, int64_t** off, char** body,
                           std::string* err) {
-  int rc;
   if (n < 0) {
     *err = "invalid request count";
     return OTM_EINVAL;
   }
   // the device side for the reads behind each pushed piece
   const size_t slots = req_sparse_slots(n, bytes);
-  if ((rc = ensure(E->d_req, req_blob_bytes(n, bytes), err))) return rc;
-  if ((rc = ensure(E->req_cnt, ((size_t)n + 1) * 8, err))) return rc;
-  if ((rc = ensure(E->req_ok, (size_t)n + 1, err))) return rc;
-  if ((rc = ensure(E->req_lat, slots * 4, err))) return rc;
-  if ((rc = ensure(E->req_lon, slots * 4, err))) return rc;
-  if ((rc = ensure(E->req_time, slots * 8, err))) return rc;
-  if ((rc = ensure(E->req_acc, slots * 4, err))) return rc;
+  TRY(E->d_req.ensure(req_blob_bytes(n, bytes), err));
+  TRY(E->req_cnt.ensure((size_t)n + 1, err));
+  TRY(E->req_ok.ensure((size_t)n + 1, err));
+  TRY(E->req_lat.ensure(slots, err));
+  TRY(E->req_lon.ensure(slots, err));
+  TRY(E->req_time.ensure(slots, err));
+  TRY(E->req_acc.ensure(slots, err));
   E->req_read = 0;
   E->req_piece = 0;
   if (!bodies) {
     // every body goes to HBM from the caller's page-locked memory: the header alone
-    if ((rc = ensure_pinned(E->h_req, req_hdr_bytes(n), err))) return rc;
+    TRY(E->h_req.ensure(req_hdr_bytes(n), err));
     *off = (int64_t*)E->h_req.p;
     *body = nullptr;
     return OTM_OK;
   }
-  if ((rc = ensure_pinned(E->h_req, req_blob_bytes(n, bytes), err))) return rc;
-  char* h = (char*)E->h_req.p;
+  TRY(E->h_req.ensure(req_blob_bytes(n, bytes), err));
+  char* h = E->h_req.p;
   std::memset(h + req_hdr_bytes(n) + bytes, 0, REQ_PAD);
   *off = (int64_t*)h;
   *body = h + req_hdr_bytes(n);
@@ -1338,19 +1169,19 @@ int engine_stage_requests(otm_engine* E, int32_t n, size_t bytes, bool bodies, i
 // are copied from there instead of the staging buffer.
 static DevBatch req_sparse(otm_engine* E) {
   DevBatch sp{};
-  sp.lat = (const float*)E->req_lat.p;
-  sp.lon = (const float*)E->req_lon.p;
-  sp.time = (const double*)E->req_time.p;
-  sp.acc = (const float*)E->req_acc.p;
+  sp.lat = E->req_lat.p;
+  sp.lon = E->req_lon.p;
+  sp.time = E->req_time.p;
+  sp.acc = E->req_acc.p;
   return sp;
 }
 
 // read requests [E->req_read, upto) of the device blob (requests.hip)
 static void read_requests(otm_engine* E, int32_t n, int32_t upto) {
   if (upto <= E->req_read) return;
-  const unsigned char* d = (const unsigned char*)E->d_req.p;
-  launch_req_read(d + req_hdr_bytes(n), (const int64_t*)d, E->req_read, upto, n, P<int64_t>(E->req_cnt),
-                  P<uint8_t>(E->req_ok), req_sparse(E), E->stream);
+  const unsigned char* d = E->d_req.p;
+  launch_req_read(d + req_hdr_bytes(n), (const int64_t*)d, E->req_read, upto, n, E->req_cnt.p, E->req_ok.p,
+                  req_sparse(E), E->stream);
   E->req_read = upto;
 }
 
@@ -1377,8 +1208,8 @@ int engine_push_requests(otm_engine* E, int32_t n, size_t bytes, size_t from, si
     HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     E->req_ev.push_back(ev);
   }
-  char* d = (char*)E->d_req.p;
-  const char* h = (const char*)E->h_req.p;
+  unsigned char* d = E->d_req.p;
+  const char* h = E->h_req.p;
   const size_t hdr = req_hdr_bytes(n);
   const hipMemcpyKind h2d = hipMemcpyHostToDevice;
   if (E->req_piece == 0) {
@@ -1415,34 +1246,28 @@ int engine_push_mark(otm_engine* E, hipEvent_t ev) {
 
 int engine_match_requests(otm_engine* E, int32_t n, size_t bytes, bool pushed, const uint8_t** ok,
                           int32_t* n_traces, std::string* err) {
-  int rc;
   hipStream_t s = E->stream;
   const size_t total = req_blob_bytes(n, bytes);
-  if ((rc = ensure_pinned(E->h_req_ok, (size_t)n + 8 + 8, err))) return rc;
-  if ((rc = ensure(E->scan_tmp, scan_tmp_bytes(n) + 256, err))) return rc;
+  TRY(E->h_req_ok.ensure((size_t)n + 8 + 8, err));
+  TRY(E->scan_tmp.ensure(scan_tmp_bytes(n) + 256, err));
   // a valid point takes at least 39 bytes (`{"lat":0,"lon":0,"time":0,"accuracy":0}`)
   // plus its separator: the batch arrays sized by that bound before the count is known
   const size_t np_max = bytes / 39 + 1;
-  if ((rc = ensure(E->in_off, ((size_t)n + 1) * 8, err))) return rc;
-  if ((rc = ensure(E->in_lat, np_max * 4, err))) return rc;
-  if ((rc = ensure(E->in_lon, np_max * 4, err))) return rc;
-  if ((rc = ensure(E->in_time, np_max * 8, err))) return rc;
-  if ((rc = ensure(E->in_acc, np_max * 4, err))) return rc;
+  DevBatch b{};
+  TRY(bind_buf(b.trace_off, E->in_off, (size_t)n + 1, err));
+  TRY(bind_buf(b.lat, E->in_lat, np_max, err));
+  TRY(bind_buf(b.lon, E->in_lon, np_max, err));
+  TRY(bind_buf(b.time, E->in_time, np_max, err));
+  TRY(bind_buf(b.acc, E->in_acc, np_max, err));
   if (!pushed) HIPCHK(big_copy(E->d_req.p, E->h_req.p, total, hipMemcpyHostToDevice, s));
   const int64_t* off = (const int64_t*)E->d_req.p;
-  int64_t* cnt = P<int64_t>(E->req_cnt);
+  int64_t* cnt = E->req_cnt.p;
   read_requests(E, n, n);  // (the requests no push read yet; n == 0: cnt[0] = 0)
   if (n == 0) HIPCHK(hipMemsetAsync(cnt, 0, 8, s));
-  scan_i64(cnt, n, E->scan_tmp.p, E->scan_tmp.cap, s);
-  DevBatch b{};
-  b.trace_off = (const int64_t*)E->in_off.p;
-  b.lat = (const float*)E->in_lat.p;
-  b.lon = (const float*)E->in_lon.p;
-  b.time = (const double*)E->in_time.p;
-  b.acc = (const float*)E->in_acc.p;
-  launch_req_compact(off, n, cnt, P<uint8_t>(E->req_ok), req_sparse(E), b, P<int64_t>(E->in_off), s);
+  scan_i64(cnt, n, E->scan_tmp.p, E->scan_tmp.cap(), s);
+  launch_req_compact(off, n, cnt, E->req_ok.p, req_sparse(E), b, E->in_off.p, s);
   // the batch's size and the flags: one synchronisation before the match
-  char* h = (char*)E->h_req_ok.p;
+  uint8_t* h = E->h_req_ok.p;
   HIPCHK(hipMemcpyAsync(h, cnt + n, 8, hipMemcpyDeviceToHost, s));
   if (n) HIPCHK(hipMemcpyAsync(h + 8, E->req_ok.p, (size_t)n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipGetLastError());
@@ -1452,7 +1277,7 @@ int engine_match_requests(otm_engine* E, int32_t n, size_t bytes, bool pushed, c
   std::memcpy(&tot, h, 8);
   b.n_traces = (int32_t)(tot >> 40);
   b.n_points = tot & (((int64_t)1 << 40) - 1);
-  *ok = (const uint8_t*)(h + 8);
+  *ok = h + 8;
   *n_traces = b.n_traces;
   if ((size_t)b.n_points > np_max) {
     *err = "request reader: point count beyond its bound";
@@ -1466,21 +1291,17 @@ int engine_match_requests(otm_engine* E, int32_t n, size_t bytes, bool pushed, c
 static int fetch_compact(otm_engine* E, int32_t* NS_, int32_t* NW_, int32_t* NR_, std::string* err) {
   hipStream_t s = E->stream;
   const int32_t NT = E->last_T;
-  int rc;
   // dense offsets: exclusive scans of the per-trace counts, then one
   // compaction pass out of the per-trace regions
-  ENS_F(f_seg_off, ((size_t)NT + 1) * 4);
-  ENS_F(f_way_off, ((size_t)NT + 1) * 4);
-  ENS_F(f_rep_off, ((size_t)NT + 1) * 4);
-  int32_t* so = P<int32_t>(E->f_seg_off);
-  int32_t* wo = P<int32_t>(E->f_way_off);
-  int32_t* ro = P<int32_t>(E->f_rep_off);
-  if ((rc = ensure_pinned(E->h_tot, 16, err))) return rc;
-  int32_t* tot = (int32_t*)E->h_tot.p;
+  int32_t *so, *wo, *ro, *tot;
+  TRY(bind_buf(so, E->f_seg_off, (size_t)NT + 1, err));
+  TRY(bind_buf(wo, E->f_way_off, (size_t)NT + 1, err));
+  TRY(bind_buf(ro, E->f_rep_off, (size_t)NT + 1, err));
+  TRY(bind_buf(tot, E->h_tot, 4, err));
   tot[0] = tot[1] = tot[2] = 0;
   if (NT && NT <= FETCH_SCAN_MAX) {
     // small batches (the batcher's rounds): the three scans in one launch
-    launch_fetch_scan(NT, P<int32_t>(E->o_seg_cnt), P<int32_t>(E->o_way_cnt), P<int32_t>(E->o_rep_cnt), so, wo, ro, s);
+    launch_fetch_scan(NT, E->o_seg_cnt.p, E->o_way_cnt.p, E->o_rep_cnt.p, so, wo, ro, s);
     HIPCHK(hipMemcpyAsync(tot, so + NT, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(tot + 1, wo + NT, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(tot + 2, ro + NT, 4, hipMemcpyDeviceToHost, s));
@@ -1492,29 +1313,23 @@ static int fetch_compact(otm_engine* E, int32_t* NS_, int32_t* NW_, int32_t* NR_
     HIPCHK(hipMemsetAsync(so + NT, 0, 4, s));
     HIPCHK(hipMemsetAsync(wo + NT, 0, 4, s));
     HIPCHK(hipMemsetAsync(ro + NT, 0, 4, s));
-    scan_i32(so, NT, E->scan_tmp.p, E->scan_tmp.cap, s);
-    scan_i32(wo, NT, E->scan_tmp.p, E->scan_tmp.cap, s);
-    scan_i32(ro, NT, E->scan_tmp.p, E->scan_tmp.cap, s);
+    scan_i32(so, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    scan_i32(wo, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    scan_i32(ro, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
     HIPCHK(hipMemcpyAsync(tot, so + NT, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(tot + 1, wo + NT, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(tot + 2, ro + NT, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(wait_batch(E, s, E->last_P));
   }
   const int32_t NS = tot[0], NW = tot[1], NR = tot[2];
-  ENS_F(f_segs, ((size_t)NS + 1) * sizeof(otm_segment));
-  ENS_F(f_ways, ((size_t)NW + 1) * 8);
-  ENS_F(f_reps, ((size_t)NR + 1) * sizeof(otm_report_rec));
-  ENS_F(f_traces, ((size_t)NT + 1) * sizeof(otm_trace_result));
+  TRY(E->f_segs.ensure((size_t)NS + 1, err));
+  TRY(E->f_ways.ensure((size_t)NW + 1, err));
+  TRY(E->f_reps.ensure((size_t)NR + 1, err));
+  TRY(E->f_traces.ensure((size_t)NT + 1, err));
   if (NT) {
     DevOut o{};
-    o.traces = E->o_traces.p;
-    o.seg_cnt = P<int32_t>(E->o_seg_cnt);
-    o.way_cnt = P<int32_t>(E->o_way_cnt);
-    o.rep_cnt = P<int32_t>(E->o_rep_cnt);
-    o.segments = E->o_segments.p;
-    o.way_ids = P<int64_t>(E->o_way_ids);
-    o.reports = E->o_reports.p;
-    launch_compact(NT, o, so, wo, ro, E->f_segs.p, P<int64_t>(E->f_ways), E->f_reps.p, E->f_traces.p, s);
+    TRY(bind_out(E, NT, E->last_P, o, err));  // (as the batch sized them)
+    launch_compact(NT, o, so, wo, ro, E->f_segs.p, E->f_ways.p, E->f_reps.p, E->f_traces.p, s);
     HIPCHK(hipGetLastError());
   }
   E->last_S = NS;
@@ -1529,12 +1344,11 @@ int engine_fetch(otm_engine* E, otm_results* out, std::string* err) {
   hipStream_t s = E->stream;
   const int32_t NT = E->last_T;
   int32_t NS, NW, NR;
-  int rc;
-  if ((rc = fetch_compact(E, &NS, &NW, &NR, err))) return rc;
-  if ((rc = ensure_pinned(E->h_traces, ((size_t)NT + 1) * sizeof(otm_trace_result), err))) return rc;
-  if ((rc = ensure_pinned(E->h_segs, ((size_t)NS + 1) * sizeof(otm_segment), err))) return rc;
-  if ((rc = ensure_pinned(E->h_reps_dense, ((size_t)NR + 1) * sizeof(otm_report_rec), err))) return rc;
-  if ((rc = ensure_pinned(E->h_ways, ((size_t)NW + 1) * 8, err))) return rc;
+  TRY(fetch_compact(E, &NS, &NW, &NR, err));
+  TRY(bind_buf(out->traces, E->h_traces, (size_t)NT + 1, err));
+  TRY(bind_buf(out->segments, E->h_segs, (size_t)NS + 1, err));
+  TRY(bind_buf(out->reports, E->h_reps_dense, (size_t)NR + 1, err));
+  TRY(bind_buf(out->way_ids, E->h_ways, (size_t)NW + 1, err));
   const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
   hipStream_t c = s;
   if (NT) HIPCHK(big_copy(E->h_traces.p, E->f_traces.p, (size_t)NT * sizeof(otm_trace_result), d2h, c));
@@ -1546,10 +1360,6 @@ int engine_fetch(otm_engine* E, otm_results* out, std::string* err) {
   out->n_segments = NS;
   out->n_reports = NR;
   out->n_way_ids = NW;
-  out->traces = (const otm_trace_result*)E->h_traces.p;
-  out->segments = (const otm_segment*)E->h_segs.p;
-  out->reports = (const otm_report_rec*)E->h_reps_dense.p;
-  out->way_ids = (const int64_t*)E->h_ways.p;
   return OTM_OK;
 }
 
@@ -1558,37 +1368,34 @@ int engine_write_responses(otm_engine* E, const int64_t** off, const uint8_t** h
   hipStream_t s = E->stream;
   const int32_t NT = E->last_T;
   int32_t NS, NW, NR;
-  int rc;
-  if ((rc = fetch_compact(E, &NS, &NW, &NR, err))) return rc;
+  TRY(fetch_compact(E, &NS, &NW, &NR, err));
   const size_t hdr_b = (size_t)NT * RESP_HDR_SLOT + 64, seg_b = resp_seg_scratch(NS, NW),
                rep_b = (size_t)NR * RESP_REP_SLOT + 64;
-  ENS_F(resp_hdr, hdr_b);
-  ENS_F(resp_seg, seg_b);
-  ENS_F(resp_rep, rep_b);
-  ENS_F(resp_hlen, ((size_t)NT + 1) * 4);
-  ENS_F(resp_slen, ((size_t)NS + 1) * 4);
-  ENS_F(resp_rlen, ((size_t)NR + 1) * 4);
-  ENS_F(resp_blen, ((size_t)NT + 1) * 8);
-  ENS_F(resp_host, (size_t)NT + 1);
+  RespWork w{};
+  TRY(bind_buf(w.hdr, E->resp_hdr, hdr_b, err));
+  TRY(bind_buf(w.seg, E->resp_seg, seg_b, err));
+  TRY(bind_buf(w.rep, E->resp_rep, rep_b, err));
+  TRY(bind_buf(w.hlen, E->resp_hlen, (size_t)NT + 1, err));
+  TRY(bind_buf(w.slen, E->resp_slen, (size_t)NS + 1, err));
+  TRY(bind_buf(w.rlen, E->resp_rlen, (size_t)NR + 1, err));
+  TRY(bind_buf(w.blen, E->resp_blen, (size_t)NT + 1, err));
+  TRY(bind_buf(w.host, E->resp_host, (size_t)NT + 1, err));
   // a body is at most its pieces plus the joins (commas, the fixed middle and end)
   const size_t blob_b = hdr_b + seg_b + rep_b + (size_t)NT * 97 + (size_t)NS + (size_t)NR;  // (+ the NULs)
-  ENS_F(resp_blob, blob_b);
-  if ((rc = ensure(E->scan_tmp, scan_tmp_bytes(NT) + 256, err))) return rc;
-  RespIn in{NT, NS, NR, (const otm_trace_result*)E->f_traces.p, (const otm_segment*)E->f_segs.p,
-            P<int64_t>(E->f_ways), (const otm_report_rec*)E->f_reps.p};
-  RespWork w{P<char>(E->resp_hdr),   P<char>(E->resp_seg),     P<char>(E->resp_rep),    P<int32_t>(E->resp_hlen),
-             P<int32_t>(E->resp_slen), P<int32_t>(E->resp_rlen), P<int64_t>(E->resp_blen), P<uint8_t>(E->resp_host)};
+  TRY(E->resp_blob.ensure(blob_b, err));
+  TRY(E->scan_tmp.ensure(scan_tmp_bytes(NT) + 256, err));
+  const RespIn in{NT, NS, NR, E->f_traces.p, E->f_segs.p, E->f_ways.p, E->f_reps.p};
   if (NT) {
     launch_resp_items(in, w, s);
     launch_resp_len(in, w, s);
-    scan_i64(w.blen, NT, E->scan_tmp.p, E->scan_tmp.cap, s);
-    launch_resp_copy(in, w, w.blen, P<char>(E->resp_blob), s);
+    scan_i64(w.blen, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    launch_resp_copy(in, w, w.blen, E->resp_blob.p, s);
   }
   // the offsets, flags and trace records, then the bodies
   const size_t off_b = ((size_t)NT + 1) * 8;
-  if ((rc = ensure_pinned(E->h_resp_meta, off_b + (size_t)NT + 8, err))) return rc;
-  if ((rc = ensure_pinned(E->h_traces, ((size_t)NT + 1) * sizeof(otm_trace_result), err))) return rc;
-  char* meta = (char*)E->h_resp_meta.p;
+  TRY(E->h_resp_meta.ensure(off_b + (size_t)NT + 8, err));
+  TRY(bind_buf(*traces, E->h_traces, (size_t)NT + 1, err));
+  char* meta = E->h_resp_meta.p;
   std::memset(meta, 0, off_b);
   if (NT) {
     HIPCHK(hipMemcpyAsync(meta, w.blen, off_b, hipMemcpyDeviceToHost, s));
@@ -1600,7 +1407,6 @@ int engine_write_responses(otm_engine* E, const int64_t** off, const uint8_t** h
   *total = ((const int64_t*)meta)[NT];
   *off = (const int64_t*)meta;
   *host = (const uint8_t*)(meta + off_b);
-  *traces = (const otm_trace_result*)E->h_traces.p;
   return OTM_OK;
 }
 
@@ -1608,10 +1414,9 @@ int engine_write_responses(otm_engine* E, const int64_t** off, const uint8_t** h
 // page-locked host memory (the caller's response arena) -- or, with dst null,
 // into the engine's own pinned buffer; *blob: where it landed
 int engine_copy_responses(otm_engine* E, char* dst, int64_t total, const char** blob, std::string* err) {
-  int rc;
   if (!dst) {
-    if ((rc = ensure_pinned(E->h_resp, (size_t)total + 16, err))) return rc;
-    dst = (char*)E->h_resp.p;
+    TRY(E->h_resp.ensure((size_t)total + 16, err));
+    dst = E->h_resp.p;
   }
   if (total) {
     HIPCHK(big_copy(dst, E->resp_blob.p, (size_t)total, hipMemcpyDeviceToHost, E->stream));
@@ -1634,7 +1439,6 @@ int engine_report_segments(otm_engine* E, int32_t T, const int64_t* trace_off, c
       *err = "every trace needs at least one point (its end time)";
       return OTM_EINVAL;
     }
-  int rc;
   // one device blob: trace_off, seg_base (per trace), time, segments,
   // seg_cnt, seg_gidx, trace_err, abort; outputs: traces, reports, rep_cnt
   const size_t b_off = ((size_t)T + 1) * 8, b_sb = ((size_t)T + 1) * 8, b_tm = (size_t)NP * 8;
@@ -1649,7 +1453,7 @@ int engine_report_segments(otm_engine* E, int32_t T, const int64_t* trace_off, c
     tot += (sz[k] + 255) & ~(size_t)255;
   }
   off[11] = tot;
-  if ((rc = ensure(E->rs_blob, tot, err))) return rc;
+  TRY(E->rs_blob.ensure(tot, err));
   std::vector<char> h(off[8], 0);
   std::memcpy(h.data() + off[0], trace_off, b_off);
   int64_t* sb = (int64_t*)(h.data() + off[1]);
@@ -1663,7 +1467,7 @@ int engine_report_segments(otm_engine* E, int32_t T, const int64_t* trace_off, c
   int32_t* gidx = (int32_t*)(h.data() + off[5]);
   for (int32_t k = 0; k < NS; ++k) gidx[k] = -1;  // no histogram for handed-in segments
   hipStream_t s = E->stream;
-  char* d = (char*)E->rs_blob.p;
+  char* d = E->rs_blob.p;
   HIPCHK(hipMemcpyAsync(d, h.data(), off[8], hipMemcpyHostToDevice, s));
   DevBatch b{};
   b.n_traces = T;
@@ -1675,13 +1479,13 @@ int engine_report_segments(otm_engine* E, int32_t T, const int64_t* trace_off, c
   w.abort = (int32_t*)(d + off[7]);
   w.ctr = nullptr;
   DevOut o{};
-  o.traces = d + off[8];
+  o.traces = (otm_trace_result*)(d + off[8]);
   o.seg_cnt = (int32_t*)(d + off[4]);
   o.rep_cnt = (int32_t*)(d + off[10]);
   o.seg_base = (int64_t*)(d + off[1]);
-  o.segments = d + off[3];
+  o.segments = (otm_segment*)(d + off[3]);
   o.seg_gidx = (int32_t*)(d + off[5]);
-  o.reports = d + off[9];
+  o.reports = (otm_report_rec*)(d + off[9]);
   o.hist = nullptr;
   o.speed_sum = nullptr;
   launch_report(b, E->drc, w, o, s, Marks{});
@@ -1696,8 +1500,13 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
   const size_t Pn = (size_t)E->last_P;
   const void* src = nullptr;
   size_t n = 0;
+  // a buffer's first `count` elements
+  auto of = [&](const auto& buf, size_t count) {
+    src = buf.p;
+    n = count * sizeof(*buf.p);
+  };
   switch (what) {
-    case 0: src = E->ncand.p; n = Pn * 4; break;
+    case 0: of(E->ncand, Pn); break;
     case 1:
     case 2:
     case 3: {
@@ -1712,11 +1521,12 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
       }
       if (!n) return OTM_OK;
       const bool rec = what != 3;
-      std::vector<char> in(Pn * KIN * (rec ? 8 : 4)), ov(Pn * KX * (rec ? 8 : 4));
-      HIPCHK(hipMemcpyAsync(in.data(), rec ? E->cand_eo.p : E->cand_em.p, in.size(), hipMemcpyDeviceToHost,
-                            E->stream));
-      HIPCHK(hipMemcpyAsync(ov.data(), rec ? E->cand_xeo.p : E->cand_xem.p, ov.size(), hipMemcpyDeviceToHost,
-                            E->stream));
+      const size_t el = rec ? sizeof(*E->cand_eo.p) : sizeof(*E->cand_em.p);
+      std::vector<char> in(Pn * KIN * el), ov(Pn * KX * el);
+      const void *din = E->cand_em.p, *dov = E->cand_xem.p;
+      if (rec) din = E->cand_eo.p, dov = E->cand_xeo.p;
+      HIPCHK(hipMemcpyAsync(in.data(), din, in.size(), hipMemcpyDeviceToHost, E->stream));
+      HIPCHK(hipMemcpyAsync(ov.data(), dov, ov.size(), hipMemcpyDeviceToHost, E->stream));
       HIPCHK(hipStreamSynchronize(E->stream));
       int32_t* d = (int32_t*)dst;
       for (size_t p = 0; p < Pn; ++p)
@@ -1727,22 +1537,22 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
         }
       return OTM_OK;
     }
-    case 4: src = E->trans_off.p; n = (Pn + 1) * 8; break;
-    case 5: src = E->trans.p; n = (size_t)E->last_trans * 4; break;
-    case 6: src = E->state.p; n = Pn * 4; break;
-    case 7: src = E->col_prev.p; n = Pn * 4; break;
-    case 8: src = E->route_dist.p; n = Pn * 4; break;
-    case 9: src = E->gc.p; n = Pn * 4; break;
-    case 10: src = E->ipos.p; n = Pn * 4; break;
+    case 4: of(E->trans_off, Pn + 1); break;
+    case 5: of(E->trans, (size_t)E->last_trans); break;
+    case 6: of(E->state, Pn); break;
+    case 7: of(E->col_prev, Pn); break;
+    case 8: of(E->route_dist, Pn); break;
+    case 9: of(E->gc, Pn); break;
+    case 10: of(E->ipos, Pn); break;
     // the last batch's inputs as the GPU request reader decoded them
     // (engine_match_requests; also a host batch of more than 2^18 points)
-    case 11: src = E->in_off.p; n = ((size_t)E->last_T + 1) * 8; break;
-    case 12: src = E->in_lat.p; n = Pn * 4; break;
-    case 13: src = E->in_lon.p; n = Pn * 4; break;
-    case 14: src = E->in_time.p; n = Pn * 8; break;
-    case 15: src = E->in_acc.p; n = Pn * 4; break;
-    case 16: src = E->chain_start.p; n = Pn; break;
-    case 17: src = E->is_col.p; n = Pn; break;
+    case 11: of(E->in_off, (size_t)E->last_T + 1); break;
+    case 12: of(E->in_lat, Pn); break;
+    case 13: of(E->in_lon, Pn); break;
+    case 14: of(E->in_time, Pn); break;
+    case 15: of(E->in_acc, Pn); break;
+    case 16: of(E->chain_start, Pn); break;
+    case 17: of(E->is_col, Pn); break;
     default: *err = "unknown debug buffer"; return OTM_EINVAL;
   }
   if (needed) *needed = n;
@@ -1773,8 +1583,7 @@ int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int6
   }
   const size_t bytes = (size_t)E->pts_n * sizeof(otm_matched_point);
   if (!bytes) return OTM_OK;
-  int rc;
-  if ((rc = ensure_pinned(E->h_pts, bytes, err))) return rc;
+  TRY(E->h_pts.ensure((size_t)E->pts_n, err));
   HIPCHK(big_copy(E->h_pts.p, E->pts.p, bytes, hipMemcpyDeviceToHost, E->stream));
   HIPCHK(wait_batch(E, E->stream, E->pts_n));
   std::memcpy(dst, E->h_pts.p, bytes);
@@ -1804,7 +1613,7 @@ int engine_spill_stats(otm_engine* E, otm_spill_stats* out) {
 
 int engine_counters(otm_engine* E, otm_work_counters* out) {
   DevCounters c;
-  if (hipMemcpy(&c, E->ctr, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return OTM_EDEVICE;
+  if (hipMemcpy(&c, E->ctr.p, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return OTM_EDEVICE;
   static_assert(sizeof(DevCounters) == sizeof(otm_work_counters), "counter layout");
   std::memcpy(out, &c, sizeof c);
   return OTM_OK;
@@ -1839,28 +1648,27 @@ int engine_flush_body(otm_engine* E, const void* dev_counts, const void* dev_spe
   HIPCHK(hipSetDevice(E->device));
   hipStream_t s = stream ? stream : E->stream;
   const int slot = flush_slot_bytes(nbins);
-  int rc;
-  ENS_F(flush_slots, (size_t)rows * (size_t)slot + 64);
-  ENS_F(flush_len, ((size_t)rows + 1) * 8);
-  ENS_F(flush_meta, sizeof(FlushMeta));
-  ENS_F(scan_tmp, scan_tmp_bytes(rows) + 256);
-  if (!E->flush_blob.p) ENS_F(flush_blob, (size_t)1 << 20);
-  if (!E->h_flush.p && (rc = ensure_pinned(E->h_flush, (size_t)1 << 20, err))) return rc;
-  if ((rc = ensure_pinned(E->h_flush_meta, 64, err))) return rc;
+  TRY(E->flush_slots.ensure((size_t)rows * (size_t)slot + 64, err));
+  TRY(E->flush_len.ensure((size_t)rows + 1, err));
+  TRY(E->flush_meta.ensure(1, err));
+  TRY(E->scan_tmp.ensure(scan_tmp_bytes(rows) + 256, err));
+  if (!E->flush_blob.p) TRY(E->flush_blob.ensure((size_t)1 << 20, err));
+  if (!E->h_flush.p) TRY(E->h_flush.ensure((size_t)1 << 20, err));
+  TRY(E->h_flush_meta.ensure(64, err));
   FlushIn in{(const uint32_t*)dev_counts, (const unsigned long long*)dev_speed_sum, E->g.g_id, rows,
              (int64_t)rank * rows, nseg, nbins};
-  int64_t* len = P<int64_t>(E->flush_len);
-  FlushMeta* meta = (FlushMeta*)E->flush_meta.p;
-  char* hm = (char*)E->h_flush_meta.p;
+  int64_t* len = E->flush_len.p;
+  FlushMeta* meta = E->flush_meta.p;
+  char* hm = E->h_flush_meta.p;
   HIPCHK(hipMemsetAsync(meta, 0, sizeof(FlushMeta), s));
-  launch_flush_rows(in, P<char>(E->flush_slots), len, meta, s);
-  scan_i64(len, rows, E->scan_tmp.p, E->scan_tmp.cap, s);
+  launch_flush_rows(in, E->flush_slots.p, len, meta, s);
+  scan_i64(len, rows, E->scan_tmp.p, E->scan_tmp.cap(), s);
   FlushMeta m{};
   int64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const int64_t cap = (int64_t)std::min(E->flush_blob.cap, E->h_flush.cap) - 16;
-    launch_flush_copy(rows, slot, P<char>(E->flush_slots), len, P<char>(E->flush_blob), cap, s);
-    launch_flush_out(P<char>(E->flush_blob), len + rows, (char*)E->h_flush.p, cap, s);
+    const int64_t cap = (int64_t)std::min(E->flush_blob.cap(), E->h_flush.cap()) - 16;
+    launch_flush_copy(rows, slot, E->flush_slots.p, len, E->flush_blob.p, cap, s);
+    launch_flush_out(E->flush_blob.p, len + rows, E->h_flush.p, cap, s);
     if (attempt == 0) {
       HIPCHK(hipMemcpyAsync(hm, meta, sizeof(FlushMeta), hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(hm + 16, len + rows, 8, hipMemcpyDeviceToHost, s));
@@ -1871,8 +1679,8 @@ int engine_flush_body(otm_engine* E, const void* dev_counts, const void* dev_spe
     std::memcpy(&total, hm + 16, 8);
     if (m.declined || total <= cap) break;
     // the body outgrew the blob: grow both and copy again (the slots stand)
-    ENS_F(flush_blob, (size_t)total + 16);
-    if ((rc = ensure_pinned(E->h_flush, (size_t)total + 16, err))) return rc;
+    TRY(E->flush_blob.ensure((size_t)total + 16, err));
+    TRY(E->h_flush.ensure((size_t)total + 16, err));
   }
   if (m.declined) {
     // a speed sum past pyrepr.h's range (2^52 x 1000): the host writes the slice
@@ -1899,7 +1707,7 @@ int engine_flush_body(otm_engine* E, const void* dev_counts, const void* dev_spe
     return OTM_ENOMEM;
   }
   std::memcpy(p, head.data(), head.size());
-  if (recs) std::memcpy(p + head.size(), (const char*)E->h_flush.p + 1, recs);
+  if (recs) std::memcpy(p + head.size(), E->h_flush.p + 1, recs);
   std::memcpy(p + head.size() + recs, "]}", 3);
   *body = p;
   *body_len = n;
@@ -2039,24 +1847,20 @@ int engine_window_flush(otm_engine* E, char** body, size_t* body_len, int64_t* n
   hipStream_t s = M0->stream;
   // the members' pairs into member 0's: in place on its device, by a peer copy
   // into a scratch pair from another
-  int rc;
   for (size_t i = 1; i < ms.size() && S > 0; ++i) {
     otm_engine* M = ms[i];
     const uint32_t* sc = (const uint32_t*)M->win_counts;
     const unsigned long long* ss = (const unsigned long long*)M->win_sums;
     if (M->device != M0->device) {
-      if ((rc = ensure(M0->win_peer_counts, cb, err))) return rc;
-      if ((rc = ensure(M0->win_peer_sums, sb, err))) return rc;
+      TRY(bind_buf(sc, M0->win_peer_counts, (size_t)S * (size_t)nbins, err));
+      TRY(bind_buf(ss, M0->win_peer_sums, (size_t)S, err));
       HIPCHK(hipMemcpyPeerAsync(M0->win_peer_counts.p, M0->device, M->win_counts, M->device, cb, s));
       HIPCHK(hipMemcpyPeerAsync(M0->win_peer_sums.p, M0->device, M->win_sums, M->device, sb, s));
-      sc = (const uint32_t*)M0->win_peer_counts.p;
-      ss = (const unsigned long long*)M0->win_peer_sums.p;
     }
     launch_flush_add((uint32_t*)M0->win_counts, sc, S * nbins, (unsigned long long*)M0->win_sums, ss, S, s);
   }
-  rc = engine_flush_body(M0, M0->win_counts, M0->win_sums, S, nbins, E->win_bin_kph, 0, 1, s, body, body_len,
-                         n_records, err);
-  if (rc) return rc;
+  TRY(engine_flush_body(M0, M0->win_counts, M0->win_sums, S, nbins, E->win_bin_kph, 0, 1, s, body, body_len,
+                        n_records, err));
   // the window goes on from zero
   for (otm_engine* M : ms) {
     if (M->device != M0->device) continue;
@@ -2209,8 +2013,7 @@ int engine_pairs_add(otm_engine* E, int64_t n, const otm_report_rec* recs, std::
   hipStream_t s = M->stream;
   constexpr int64_t CHUNK = 1 << 20;
   std::vector<PairIn> host((size_t)std::min(n, CHUNK));
-  int rc;
-  if ((rc = ensure(M->pairs_in, host.size() * sizeof(PairIn), err))) return rc;
+  TRY(M->pairs_in.ensure(host.size(), err));
   PairTab t;
   {
     std::lock_guard<std::mutex> hl(M->hist_mu);
@@ -2224,7 +2027,7 @@ int engine_pairs_add(otm_engine* E, int64_t n, const otm_report_rec* recs, std::
                                r.queue_length, r.flags, 0u};
     }
     HIPCHK(hipMemcpyAsync(M->pairs_in.p, host.data(), (size_t)m * sizeof(PairIn), hipMemcpyHostToDevice, s));
-    launch_pairs_add(t, (const PairIn*)M->pairs_in.p, m, s);
+    launch_pairs_add(t, M->pairs_in.p, m, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));  // (the staging vector and pairs_in are used again)
   }
@@ -2263,7 +2066,6 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
   std::lock_guard<std::mutex> lk(M0->mu);
   HIPCHK(hipSetDevice(M0->device));
   hipStream_t s = M0->stream;
-  int rc;
   PairTab T = M0->pairs_tab;
   unsigned long long hc[PAIR_C_WORDS] = {};  // a group's members' counters
   if (ms.size() > 1) {
@@ -2273,12 +2075,9 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
     D.max_keys = cfg.max_keys * (int64_t)ms.size();
     D.log2 = pairs_log2(D.max_keys);
     const size_t dslots = (size_t)1 << D.log2;
-    if ((rc = ensure(M0->pm_key, dslots * sizeof(unsigned long long), err))) return rc;
-    if ((rc = ensure(M0->pm_val, dslots * sizeof(PairVal), err))) return rc;
-    if ((rc = ensure(M0->pm_ctr, 64, err))) return rc;
-    D.key = P<unsigned long long>(M0->pm_key);
-    D.val = P<PairVal>(M0->pm_val);
-    D.ctr = P<unsigned long long>(M0->pm_ctr);
+    TRY(bind_buf(D.key, M0->pm_key, dslots, err));
+    TRY(bind_buf(D.val, M0->pm_val, dslots, err));
+    TRY(bind_buf(D.ctr, M0->pm_ctr, 8, err));
     launch_pairs_clear(D, s);
     for (size_t i = 0; i < ms.size(); ++i) {
       otm_engine* M = ms[i];
@@ -2287,12 +2086,10 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
       const unsigned long long* sk = S.key;
       const PairVal* sv = S.val;
       if (M->device != M0->device) {
-        if ((rc = ensure(M0->pp_key, sslots * sizeof(unsigned long long), err))) return rc;
-        if ((rc = ensure(M0->pp_val, sslots * sizeof(PairVal), err))) return rc;
+        TRY(bind_buf(sk, M0->pp_key, sslots, err));
+        TRY(bind_buf(sv, M0->pp_val, sslots, err));
         HIPCHK(hipMemcpyPeerAsync(M0->pp_key.p, M0->device, S.key, M->device, sslots * sizeof(unsigned long long), s));
         HIPCHK(hipMemcpyPeerAsync(M0->pp_val.p, M0->device, S.val, M->device, sslots * sizeof(PairVal), s));
-        sk = P<unsigned long long>(M0->pp_key);
-        sv = P<PairVal>(M0->pp_val);
       }
       launch_pairs_merge(D, sk, sv, (int64_t)sslots, s);
       // (the devices are idle: a plain copy; a group's flush is not the one-sync path)
@@ -2304,38 +2101,37 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
   }
   const int64_t cap = T.max_keys;
   const size_t sort_bytes = pairs_sort_tmp_bytes(cap);
-  if ((rc = ensure(M0->pairs_ckey, (size_t)cap * 8, err))) return rc;
-  if ((rc = ensure(M0->pairs_skey, (size_t)cap * 8, err))) return rc;
-  if ((rc = ensure(M0->pairs_cidx, (size_t)cap * 4, err))) return rc;
-  if ((rc = ensure(M0->pairs_sidx, (size_t)cap * 4, err))) return rc;
-  if ((rc = ensure(M0->pairs_sort_tmp, sort_bytes + 256, err))) return rc;
-  if ((rc = ensure(M0->pairs_meta, 64, err))) return rc;
-  if ((rc = ensure(M0->flush_slots, (size_t)cap * PAIR_SLOT_BYTES + 64, err))) return rc;
-  if ((rc = ensure(M0->flush_len, ((size_t)cap + 1) * 8, err))) return rc;
-  if ((rc = ensure(M0->scan_tmp, scan_tmp_bytes(cap) + 256, err))) return rc;
-  if (!M0->flush_blob.p && (rc = ensure(M0->flush_blob, (size_t)1 << 20, err))) return rc;
-  if (!M0->h_flush.p && (rc = ensure_pinned(M0->h_flush, (size_t)1 << 20, err))) return rc;
-  if ((rc = ensure_pinned(M0->h_flush_meta, 128, err))) return rc;
-  unsigned long long* ckey = P<unsigned long long>(M0->pairs_ckey);
+  unsigned long long *ckey, *skey;
+  uint32_t *cidx, *sidx;
+  int64_t* len;
+  char *slots, *hm;
+  TRY(bind_buf(ckey, M0->pairs_ckey, (size_t)cap, err));
+  TRY(bind_buf(skey, M0->pairs_skey, (size_t)cap, err));
+  TRY(bind_buf(cidx, M0->pairs_cidx, (size_t)cap, err));
+  TRY(bind_buf(sidx, M0->pairs_sidx, (size_t)cap, err));
+  TRY(M0->pairs_sort_tmp.ensure(sort_bytes + 256, err));
+  TRY(M0->pairs_meta.ensure(64, err));
+  TRY(bind_buf(slots, M0->flush_slots, (size_t)cap * PAIR_SLOT_BYTES + 64, err));
+  TRY(bind_buf(len, M0->flush_len, (size_t)cap + 1, err));
+  TRY(M0->scan_tmp.ensure(scan_tmp_bytes(cap) + 256, err));
+  if (!M0->flush_blob.p) TRY(M0->flush_blob.ensure((size_t)1 << 20, err));
+  if (!M0->h_flush.p) TRY(M0->h_flush.ensure((size_t)1 << 20, err));
+  TRY(bind_buf(hm, M0->h_flush_meta, 128, err));
   PairMeta* meta = (PairMeta*)M0->pairs_meta.p;
-  unsigned long long* nocc = (unsigned long long*)((char*)M0->pairs_meta.p + sizeof(PairMeta));
-  int64_t* len = P<int64_t>(M0->flush_len);
-  char* hm = (char*)M0->h_flush_meta.p;
+  unsigned long long* nocc = (unsigned long long*)(M0->pairs_meta.p + sizeof(PairMeta));
   HIPCHK(hipMemsetAsync(ckey, 0xFF, (size_t)cap * 8, s));
   HIPCHK(hipMemsetAsync(M0->pairs_meta.p, 0, 64, s));
-  launch_pairs_compact(T, ckey, P<uint32_t>(M0->pairs_cidx), nocc, s);
-  pairs_sort(ckey, P<unsigned long long>(M0->pairs_skey), P<uint32_t>(M0->pairs_cidx), P<uint32_t>(M0->pairs_sidx),
-             cap, M0->pairs_sort_tmp.p, sort_bytes, s);
-  launch_pairs_rows(T, P<unsigned long long>(M0->pairs_skey), P<uint32_t>(M0->pairs_sidx), cap, M0->g.g_id,
-                    cfg.privacy, cfg.origin, P<char>(M0->flush_slots), len, meta, s);
-  scan_i64(len, cap, M0->scan_tmp.p, M0->scan_tmp.cap, s);
+  launch_pairs_compact(T, ckey, cidx, nocc, s);
+  pairs_sort(ckey, skey, cidx, sidx, cap, M0->pairs_sort_tmp.p, sort_bytes, s);
+  launch_pairs_rows(T, skey, sidx, cap, M0->g.g_id, cfg.privacy, cfg.origin, slots, len, meta, s);
+  scan_i64(len, cap, M0->scan_tmp.p, M0->scan_tmp.cap(), s);
   PairMeta m{};
   unsigned long long c0[PAIR_C_WORDS];
   int64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const int64_t bcap = (int64_t)std::min(M0->flush_blob.cap, M0->h_flush.cap) - 16;
-    launch_flush_copy(cap, PAIR_SLOT_BYTES, P<char>(M0->flush_slots), len, P<char>(M0->flush_blob), bcap, s);
-    launch_flush_out(P<char>(M0->flush_blob), len + cap, (char*)M0->h_flush.p, bcap, s);
+    const int64_t bcap = (int64_t)std::min(M0->flush_blob.cap(), M0->h_flush.cap()) - 16;
+    launch_flush_copy(cap, PAIR_SLOT_BYTES, slots, len, M0->flush_blob.p, bcap, s);
+    launch_flush_out(M0->flush_blob.p, len + cap, M0->h_flush.p, bcap, s);
     if (attempt == 0) {
       HIPCHK(hipMemcpyAsync(hm, meta, sizeof(PairMeta), hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(hm + 32, len + cap, 8, hipMemcpyDeviceToHost, s));
@@ -2348,8 +2144,8 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
     std::memcpy(c0, hm + 64, sizeof c0);
     if (total <= bcap) break;
     // the body outgrew the blob: grow both and copy again (the slots stand)
-    if ((rc = ensure(M0->flush_blob, (size_t)total + 16, err))) return rc;
-    if ((rc = ensure_pinned(M0->h_flush, (size_t)total + 16, err))) return rc;
+    TRY(M0->flush_blob.ensure((size_t)total + 16, err));
+    TRY(M0->h_flush.ensure((size_t)total + 16, err));
   }
   // the head and tail around the records (each came with a leading comma)
   const std::string head = "{\"mode\":\"auto\",\"bucket_s\":" + std::to_string(cfg.bucket_s) +
@@ -2363,7 +2159,7 @@ int engine_pairs_flush(otm_engine* E, char** body, size_t* body_len, otm_pairs_s
     return OTM_ENOMEM;
   }
   std::memcpy(p, head.data(), head.size());
-  if (recs) std::memcpy(p + head.size(), (const char*)M0->h_flush.p + 1, recs);
+  if (recs) std::memcpy(p + head.size(), M0->h_flush.p + 1, recs);
   std::memcpy(p + head.size() + recs, "]}", 3);
   // the window goes on from an empty table
   auto fail_free = [&](hipError_t e, const char* what) {

@@ -11,6 +11,8 @@
 #include <thread>
 #include <vector>
 
+#include "buffers.h"
+#include "flush.h"
 #include "kernels.h"
 #include "otm_internal.h"
 #include "otmatch.h"
@@ -43,6 +45,11 @@ struct H2DOrder {
 }  // namespace otm
 
 struct otm_engine {
+  // the buffers below free themselves on the engine's device (engine_free has
+  // released what is not a buffer: streams, events, the graph, the windows)
+  ~otm_engine() {
+    if (members.empty() && device >= 0) (void)hipSetDevice(device);
+  }
   const otm_engine* parent = nullptr;  // a clone shares its parent's graph and index (otm_engine_clone)
   // a multi-device engine (otm_engine_create with ndev > 1, group.cpp): one
   // member engine per device and no GPU state of its own; host batches are split
@@ -57,7 +64,7 @@ struct otm_engine {
   std::vector<otm_segment> g_segs;
   std::vector<otm_report_rec> g_reps;
   std::vector<int64_t> g_ways;
-  int device = 0;
+  int device = -1;  // (-1: engine_init / engine_clone has not run)
   std::atomic<int> n_clones{0};  // clones made of this engine (their stream slots; clones race with the async start)
   hipStream_t stream = nullptr;
   hipEvent_t sync_ev = nullptr;  // blocking-sync event of large batches' host waits
@@ -97,36 +104,61 @@ struct otm_engine {
   otm::DevReportCfg drc{};
   std::mutex mu;  // one batch at a time per engine
 
-  struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-  };
-  // batch inputs (host batches are staged here)
-  Buf in_off, in_lat, in_lon, in_time, in_acc, in_blob;
-  // work
-  Buf pt_trace, is_col, prevc, nextc, gc, ncand, cand_eo, cand_em, cand_xeo, cand_xem, probe, col_prev, kq_prev, vmeta, colrec, colrec_pos, trans_off, trans, bp, state, chosen,
-      chain_start, route_dist, ipos, path_off, path_len, path_pool, trace_err, spill_list1, spill_list2,
-      counters_i32, scan_tmp, snap;
-  Buf big_key, big_lab, big_inq, big_fr, big_ins, big_prev;
-  Buf huge_key, huge_lab, huge_inq, huge_fr, huge_ins, huge_prev, spill_list3;
+  // ---- the engine's arrays (buffers.h), one allocation each, grouped by what
+  // they serve; ~otm_engine frees them
+  // batch inputs (host batches are staged here; h_in: their pinned staging)
+  otm::DevBuf<int64_t> in_off;
+  otm::DevBuf<float> in_lat, in_lon, in_acc;
+  otm::DevBuf<double> in_time;
+  otm::DevBuf<char> in_blob;
+  otm::PinBuf<char> h_in;
+  // per-point and per-trace work (DevWork; abort_flag: capacity overflow of the batch in flight)
+  otm::DevBuf<int32_t> pt_trace, prevc, nextc, ncand, col_prev, kq_prev, colrec_pos, state, path_off, path_len, path_pool,
+      trace_err, spill_list1, spill_list2, spill_list3, counters_i32, abort_flag;
+  otm::DevBuf<uint8_t> is_col, vmeta, bp, chain_start;
+  otm::DevBuf<float> gc, cand_em, cand_xem, trans, route_dist, ipos;
+  otm::DevBuf<int2> cand_eo, cand_xeo, chosen;
+  otm::DevBuf<float4> probe;
+  otm::DevBuf<int4> colrec;
+  otm::DevBuf<int64_t> trans_off;
+  otm::DevBuf<otm::SnapBuf> snap;
+  otm::DevBuf<char> scan_tmp;
+  otm::PinBuf<otm::BatchStatus> h_status;
+  otm::DevBuf<otm::DevCounters> ctr, ctr_save;
+  int64_t trans_cap = 0;                        // floats in `trans` (grown on overflow)
+  bool caps_read = false, caps_pinned = false;  // OTM_TRANS_CAP / OTM_POOL_CAP
+  // the search and candidate tiers' tables (big_fr / huge_fr: two frontier arrays a table)
+  otm::DevBuf<uint32_t> big_key, big_inq, big_fr, big_ins, huge_key, huge_inq, huge_fr, huge_ins, cbig_key;
+  otm::DevBuf<unsigned long long> big_lab, huge_lab, cbig_val, cbig_skey;
+  otm::DevBuf<int32_t> big_prev, huge_prev;
   int32_t huge_log2 = 0;  // huge search tier: 2^huge_log2 slots per table (0: none yet; grown on demand)
   int32_t huge_ready_log2 = 0;  // the layout the huge tables were last cleared for
-  Buf cbig_key, cbig_val, cbig_skey;
   int32_t cand_log2 = 0;  // candidate HBM tier: 2^cand_log2 slots per table (0: none yet; grown on demand)
   int32_t huge_final = 0, cand_final = 0;  // the tier's tables cannot grow: overflows fail their traces
   int32_t last_attempts = 0;  // runs of the last batch (otm_spill_stats::attempts)
   int32_t last_resumes = 0;   // ... of them resumed from a grown tier (otm_spill_stats::resumed)
-  Buf ord_tile, ord_cnt, ord_cursor, ord_grp, ord_item;  // spatial work order
-  Buf abort_flag;                                       // capacity overflow of the batch in flight
-  Buf rs_blob;                                          // otm_report_segments_device in/out
-  int64_t trans_cap = 0;                                // floats in `trans` (grown on overflow)
-  bool caps_read = false, caps_pinned = false;          // OTM_TRANS_CAP / OTM_POOL_CAP
-  // outputs
-  Buf o_traces, o_seg_cnt, o_way_cnt, o_rep_cnt, seg_ub, o_segments, o_seg_gidx, o_way_ids, o_reports;
-  // dense copies made by engine_fetch
-  Buf f_seg_off, f_way_off, f_rep_off, f_segs, f_ways, f_reps, f_traces;
-  otm::DevCounters* ctr = nullptr;
-  otm::DevCounters* ctr_save = nullptr;
+  // spatial work order (DevOrder)
+  otm::DevBuf<uint16_t> ord_tile;
+  otm::DevBuf<int32_t> ord_cnt, ord_cursor, ord_grp, ord_item;
+  // outputs (DevOut; seg_ub: its seg_base)
+  otm::DevBuf<otm_trace_result> o_traces;
+  otm::DevBuf<int32_t> o_seg_cnt, o_way_cnt, o_rep_cnt, o_seg_gidx;
+  otm::DevBuf<int64_t> seg_ub, o_way_ids;
+  otm::DevBuf<otm_segment> o_segments;
+  otm::DevBuf<otm_report_rec> o_reports;
+  otm::DevBuf<char> rs_blob;  // otm_report_segments_device in/out
+  // dense copies made by engine_fetch, and the host copies of the last fetched
+  // results (pinned: the D2H copies run at PCIe speed without a staging hop)
+  otm::DevBuf<int32_t> f_seg_off, f_way_off, f_rep_off;
+  otm::DevBuf<otm_segment> f_segs;
+  otm::DevBuf<int64_t> f_ways;
+  otm::DevBuf<otm_report_rec> f_reps;
+  otm::DevBuf<otm_trace_result> f_traces;
+  otm::PinBuf<otm_trace_result> h_traces;
+  otm::PinBuf<otm_segment> h_segs;
+  otm::PinBuf<otm_report_rec> h_reps_dense;
+  otm::PinBuf<int64_t> h_ways;
+  otm::PinBuf<int32_t> h_tot;
   bool counting = false;
   // histogram (caller-owned device memory).  Clones read their parent's
   // binding at each batch (under the parent's hist_mu), so a rebind reaches them.
@@ -141,13 +173,16 @@ struct otm_engine {
   int32_t last_S = 0, last_W = 0;
   int64_t last_trans = 0;
   int32_t pool_cap = 0;
-  // host copies of the last fetched results
-  // (pinned: the D2H copies run at PCIe speed without a staging hop)
-  Buf h_traces, h_segs, h_reps_dense, h_ways, h_tot, h_in, h_status;
   // request bodies read on the GPU (engine_match_requests): the pinned staging
-  // blob (offsets, then bytes), its device copy, per-request counts and flags
-  Buf h_req, d_req, req_cnt, req_ok, h_req_ok;
-  Buf req_lat, req_lon, req_time, req_acc;  // the reader's sparse point slots (requests.hip)
+  // blob (offsets, then bytes), its device copy, per-request counts and flags,
+  // the reader's sparse point slots (requests.hip)
+  otm::PinBuf<char> h_req;
+  otm::DevBuf<unsigned char> d_req;
+  otm::DevBuf<int64_t> req_cnt;
+  otm::DevBuf<uint8_t> req_ok;
+  otm::PinBuf<uint8_t> h_req_ok;
+  otm::DevBuf<float> req_lat, req_lon, req_acc;
+  otm::DevBuf<double> req_time;
   int32_t req_read = 0;                     // requests of the staged batch read so far
   hipStream_t req_copy = nullptr;           // the request pieces' H2D copies (created at first use)
   double t_read_done = 0.0;                 // (OTM_JSON_PROFILE) when the last request batch's read synced
@@ -161,13 +196,18 @@ struct otm_engine {
   size_t req_piece = 0;                     // pieces of the staged batch pushed so far
   // response bodies written on the GPU (engine_write_responses): piece slots,
   // lengths, the dense blob, and its pinned host copy with offsets and flags
-  Buf resp_hdr, resp_seg, resp_rep, resp_hlen, resp_slen, resp_rlen, resp_blen, resp_host, resp_blob;
-  Buf h_resp, h_resp_meta;
+  otm::DevBuf<char> resp_hdr, resp_seg, resp_rep, resp_blob;
+  otm::DevBuf<int32_t> resp_hlen, resp_slen, resp_rlen;
+  otm::DevBuf<int64_t> resp_blen;
+  otm::DevBuf<uint8_t> resp_host;
+  otm::PinBuf<char> h_resp, h_resp_meta;
   // the datastore flush body written on the GPU (engine_flush_body, flush.hip):
   // the rows' slots and lengths, the dense blob, the call's counters, and the
   // blob's page-locked host copy; kept at the size they grew to
-  Buf flush_slots, flush_len, flush_blob, flush_meta;
-  Buf h_flush, h_flush_meta;
+  otm::DevBuf<char> flush_slots, flush_blob;
+  otm::DevBuf<int64_t> flush_len;
+  otm::DevBuf<otm::FlushMeta> flush_meta;
+  otm::PinBuf<char> h_flush, h_flush_meta;
   // an engine-owned window (otm_window_begin, on a parent engine or on each
   // member of a multi-device engine): library-owned counts and speed sums,
   // bound as otm_hist_bind_ex binds a caller's.  On a multi-device engine
@@ -179,7 +219,8 @@ struct otm_engine {
   float win_bin_kph = 0.0f;
   void* win_counts = nullptr;
   void* win_sums = nullptr;
-  Buf win_peer_counts, win_peer_sums;
+  otm::DevBuf<uint32_t> win_peer_counts;
+  otm::DevBuf<unsigned long long> win_peer_sums;
   // a pair window (otm_pairs_begin, pairs.h; on a parent engine or on each
   // member of a multi-device engine): the table in library-owned HBM, handed
   // to every batch's DevOut under hist_mu as the histogram binding is.  On a
@@ -191,8 +232,11 @@ struct otm_engine {
   bool pairs_open = false;
   otm_pairs_cfg pairs_cfg{};
   otm::PairTab pairs_tab{};
-  Buf pairs_ckey, pairs_skey, pairs_cidx, pairs_sidx, pairs_sort_tmp, pairs_meta, pairs_in;
-  Buf pm_key, pm_val, pm_ctr, pp_key, pp_val;
+  otm::DevBuf<unsigned long long> pairs_ckey, pairs_skey, pm_key, pm_ctr, pp_key;
+  otm::DevBuf<uint32_t> pairs_cidx, pairs_sidx;
+  otm::DevBuf<char> pairs_sort_tmp, pairs_meta;  // pairs_meta: PairMeta, then the occupied-slot count
+  otm::DevBuf<otm::PairIn> pairs_in;
+  otm::DevBuf<otm::PairVal> pm_val, pp_val;
   std::vector<std::pair<uint64_t, int32_t>> pairs_rows;  // (segment id, row) ascending, built at the first add
   // timing
   bool timing = false;
@@ -237,13 +281,14 @@ struct otm_engine {
   std::mutex split_mu;
   otm::H2DOrder split_order;
   std::atomic<int> last_split{1};  // the chunks of the last otm_report_batch (otm_debug_last_split)
-  // matched points (otm_set_points, DESIGN.md §3 rule 7c; last, so every other member lies where it
-  // lay): off, a batch launches and allocates nothing for them.  pts: otm_matched_point[last_P] of the
+  // matched points (otm_set_points, DESIGN.md §3 rule 7c): off, a batch launches and allocates
+  // nothing for them.  pts: otm_matched_point[last_P] of the
   // last batch that ran with the switch on (pts_n its count, -1: none); h_pts: the pinned staging of
   // otm_fetch_points; g_pts: a multi-device engine's joined records (g_pts_n as pts_n)
   bool points_on = false;
   int64_t pts_n = -1, g_pts_n = -1;
-  Buf pts, h_pts;
+  otm::DevBuf<otm_matched_point> pts;
+  otm::PinBuf<otm_matched_point> h_pts;
   std::vector<otm_matched_point> g_pts;
 };
 

@@ -402,16 +402,16 @@ __host__ __device__ __forceinline__ SpillRef spill_of(const DevWork& w) {
 // them.
 struct DevOut {
   // per trace
-  void* traces;          // otm_trace_result[T] (seg_off / rep_off = region start)
+  otm_trace_result* traces;  // [T] (seg_off / rep_off = region start)
   int32_t* seg_cnt;      // [T+1] segments per trace
   int32_t* way_cnt;      // [T+1] way ids per trace
   int32_t* rep_cnt;      // [T+1] reports per trace
   int64_t* seg_base;     // [T+1] exclusive scan of the per-trace bound
   // regions (capacity = bound total)
-  void* segments;        // otm_segment[]
+  otm_segment* segments;  // []
   int32_t* seg_gidx;     // [] segment index in graph (-1 none)
   int64_t* way_ids;      // []
-  void* reports;         // otm_report_rec[]
+  otm_report_rec* reports;  // []
   uint32_t* hist;        // [n_segments * nbins] or nullptr
   unsigned long long* speed_sum;  // [n_segments] sum of report speeds, 1/1000 km/h, or nullptr
   int nbins;
@@ -491,7 +491,8 @@ void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, 
 // fetch-time compaction of the per-trace regions into dense arrays; offsets
 // are the exclusive scans of seg_cnt / way_cnt / rep_cnt
 void launch_compact(int32_t n_traces, const DevOut& o, const int32_t* seg_off, const int32_t* way_off,
-                    const int32_t* rep_off, void* segs_out, int64_t* ways_out, void* reps_out, void* traces_out,
+                    const int32_t* rep_off, otm_segment* segs_out, int64_t* ways_out, otm_report_rec* reps_out,
+                    otm_trace_result* traces_out,
                     hipStream_t s);
 // index build: pass 0 counts rows (row_cnt), pass 1 inserts them into the
 // row tables (slot array pre-filled with 0xFF)

@@ -4211,7 +4211,7 @@ __global__ __launch_bounds__(TB, (PT <= 128 ? 4 : 2)) void k_segments(DevGraph g
       sr.way_off = base + S.g_w0[si];
       sr.way_cnt = S.g_w0[si + 1] - S.g_w0[si];
       sr.pad = 0u;
-      ((otm_segment*)o.segments)[base + si] = sr;
+      o.segments[base + si] = sr;
       o.seg_gidx[base + si] = sg;
     }
     if (lane == 0) {
@@ -4321,7 +4321,7 @@ __global__ __launch_bounds__(TB) void k_queue(DevBatch b, DevWork w, DevOut o, f
     const int64_t a = b.trace_off[t];
     const int n = (int)(b.trace_off[t + 1] - a);
     const int32_t ns = o.seg_cnt[t];
-    otm_segment* SG = (otm_segment*)o.segments + (int32_t)o.seg_base[t];
+    otm_segment* SG = o.segments + (int32_t)o.seg_base[t];
     for (int si = lane; si < ns; si += TB) {
       const otm_segment s = SG[si];
       if (s.segment_id < 0 || s.length < 0 || n <= 0) continue;
@@ -4478,7 +4478,7 @@ __device__ __forceinline__ void report_pair(const DevOut& o, int32_t seg_off, in
                                             const otm_report_rec& rep) {
   int32_t gn = -1;
   if (rep.next_id >= 0) {
-    const otm_segment* S = (const otm_segment*)o.segments + seg_off;
+    const otm_segment* S = o.segments + seg_off;
     int32_t j = ps + 1;
     while (j < seg_cnt && (S[j].flags & OTM_SEG_INTERNAL)) ++j;
     if (j < seg_cnt) gn = o.seg_gidx[seg_off + j];
@@ -4504,15 +4504,15 @@ __global__ __launch_bounds__(256, OTM_REPORT_WAVES) void k_report(DevBatch b, De
   r.seg_off = (int32_t)o.seg_base[t];
   r.seg_cnt = o.seg_cnt[t];
   r.rep_off = r.seg_off;
-  otm_report_rec* REP = (otm_report_rec*)o.reports + r.rep_off;
-  const int nrep = report_walk(t, b, rc, w, (const otm_segment*)o.segments + r.seg_off, r, REP);
+  otm_report_rec* REP = o.reports + r.rep_off;
+  const int nrep = report_walk(t, b, rc, w, o.segments + r.seg_off, r, REP);
   for (int k = 0; k < nrep; ++k) report_pass(o, r.seg_off, r.seg_cnt, REP[k]);
   r.rep_cnt = nrep;
   if (w.ctr && r.code == 200) {
     cadd(&w.ctr->segments_out, (unsigned long long)r.seg_cnt);
     cadd(&w.ctr->reports_out, (unsigned long long)nrep);
   }
-  ((otm_trace_result*)o.traces)[t] = r;
+  o.traces[t] = r;
   o.rep_cnt[t] = r.rep_cnt;
 }
 
@@ -4535,8 +4535,8 @@ __global__ __launch_bounds__(TB) void k_report_wave(DevBatch b, DevReportCfg rc,
     r.seg_off = (int32_t)o.seg_base[t];
     r.seg_cnt = o.seg_cnt[t];
     r.rep_off = r.seg_off;
-    const otm_segment* G = (const otm_segment*)o.segments + r.seg_off;
-    otm_report_rec* REP = (otm_report_rec*)o.reports + r.rep_off;
+    const otm_segment* G = o.segments + r.seg_off;
+    otm_report_rec* REP = o.reports + r.rep_off;
     const bool fits = r.seg_cnt <= REPW_CAP;
     if (fits && r.error_kind == 0) {
       const unsigned long long* gw = (const unsigned long long*)G;
@@ -4551,7 +4551,7 @@ __global__ __launch_bounds__(TB) void k_report_wave(DevBatch b, DevReportCfg rc,
         cadd(&w.ctr->segments_out, (unsigned long long)r.seg_cnt);
         cadd(&w.ctr->reports_out, (unsigned long long)nrep);
       }
-      ((otm_trace_result*)o.traces)[t] = r;
+      o.traces[t] = r;
       o.rep_cnt[t] = nrep;
       __threadfence_block();  // the reports, for the other lanes' histogram pass
     }
@@ -4682,9 +4682,9 @@ __global__ __launch_bounds__(TB) void k_compact(int32_t n_traces, DevOut o, cons
                                                 const int32_t* rep_off, otm_segment* so, int64_t* wo,
                                                 otm_report_rec* ro, otm_trace_result* to) {
   const int lane = threadIdx.x;
-  const otm_trace_result* TR = (const otm_trace_result*)o.traces;
-  const otm_segment* SI = (const otm_segment*)o.segments;
-  const otm_report_rec* RI = (const otm_report_rec*)o.reports;
+  const otm_trace_result* TR = o.traces;
+  const otm_segment* SI = o.segments;
+  const otm_report_rec* RI = o.reports;
   for (int32_t t = blockIdx.x; t < n_traces; t += gridDim.x) {
     const int32_t base = TR[t].seg_off;  // the region start k_report recorded
     const int32_t ns = o.seg_cnt[t], nw = o.way_cnt[t], nr = o.rep_cnt[t];
@@ -5228,11 +5228,10 @@ void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, 
                                          g, b, p, w, tb));
 }
 void launch_compact(int32_t n_traces, const DevOut& o, const int32_t* seg_off, const int32_t* way_off,
-                    const int32_t* rep_off, void* segs_out, int64_t* ways_out, void* reps_out, void* traces_out,
-                    hipStream_t s) {
+                    const int32_t* rep_off, otm_segment* segs_out, int64_t* ways_out, otm_report_rec* reps_out,
+                    otm_trace_result* traces_out, hipStream_t s) {
   hipLaunchKernelGGL(k_compact, dim3(grid_for(n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, n_traces, o, seg_off, way_off,
-                     rep_off, (otm_segment*)segs_out, ways_out, (otm_report_rec*)reps_out,
-                     (otm_trace_result*)traces_out);
+                     rep_off, segs_out, ways_out, reps_out, traces_out);
 }
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s,
                    const Marks& mk) {
