@@ -408,6 +408,72 @@ int otm_points_info(const otm_engine* eng, int* on);
 int otm_fetch_points(otm_engine* eng, otm_matched_point* dst, int64_t cap, int64_t* n_points);
 int otm_points_device(otm_engine* eng, const void** dev, int64_t* n_points);
 
+/* Matched route (extension, DESIGN.md §3 rule 7d): the directed edges each
+ * trace of the last binary-level batch drove, in order -- one record per
+ * traversed edge, the traversals rule 7 groups into segments, written on the
+ * GPU (k_traversals) after the segments.  Off by default, per handle: with the
+ * switch off a match launches and allocates nothing more.  A clone inherits its
+ * parent's value when it is made; a multi-device engine passes the call to
+ * every member.
+ *   A chain of >= 2 states gives: its first state's edge from that state's
+ *   offset, every edge of every step's route whole, and its last edge up to
+ *   the largest offset its states reached.  A traversal that would start on a
+ *   node candidate is not emitted.  A chain of one state, a trace answered 500
+ *   and a chain that never leaves a node give nothing.
+ *   Inside a chain the edge's end node is the next edge's start node, and
+ *   exit_time is bit-equal to the next record's enter_time and end_shape_index
+ *   equals the next begin_shape_index -- except across a state on a node
+ *   candidate, whose own traversal is not emitted: there the record before
+ *   ends at that state's time and point, the record after begins at the last
+ *   point that still stands on the node, and exit_time <= enter_time (the time
+ *   the vehicle waited on the node).  Times and shape indices are the ones the
+ *   trace's segments were made of.
+ * Only the three binary-level calls write records.  With the switch on, a JSON,
+ * request or batcher batch on the same handle launches and allocates nothing
+ * for them; where it uses the handle's own buffers (as any failed batch does)
+ * it leaves nothing to fetch until the next binary-level batch: a fetch then
+ * answers OTM_EINVAL, never another batch's records. */
+#define OTM_TV_CHAIN_START 1u    /* the first emitted traversal of a chain */
+#define OTM_TV_CHAIN_END 2u      /* the last one */
+#define OTM_TV_FROM_START 4u     /* begin_offset == 0 */
+#define OTM_TV_TO_END 8u         /* end_offset is the edge's length, bit for bit */
+#define OTM_TV_INTERNAL 16u      /* an internal (intersection) edge without OSMLR segment: its otm_segment's OTM_SEG_INTERNAL */
+#define OTM_TV_SEGMENT_FIRST 32u /* it starts a new otm_segment */
+typedef struct otm_traversal { /* 56 bytes */
+  int32_t edge;               /* directed edge id of the graph file */
+  uint32_t flags;             /* OTM_TV_* */
+  float begin_offset;         /* metres from the edge's start; 0 except on a chain's first traversal */
+  float end_offset;           /* the edge's length (bit-equal) except on a chain's last traversal */
+  double enter_time, exit_time;
+  int32_t begin_shape_index, end_shape_index; /* trace-relative, as otm_segment's */
+  int32_t segment;            /* which of the trace's segments it was grouped into:
+                                 otm_results.segments[traces[t].seg_off + segment] */
+  int32_t pad;                /* 0 */
+  int64_t way_id;
+} otm_traversal;
+/* otm_set_traversals: the switch (on != 0).  otm_traversals_info: its value.
+ * otm_traversals_size: the trace count and the record count of the batch the
+ * fetch answers for -- trav_off needs *n_traces + 1 elements, dst *n; a caller
+ * that does not know which batch the handle ran last (a member of a
+ * multi-device engine: its share of the group's batch) sizes from this.
+ * otm_fetch_traversals answers for the handle's last otm_match_soa,
+ * otm_match_compact or otm_match_device batch, any number of times with the
+ * same bytes: *n records, dense and in trace order, into dst[cap], trace t's at
+ * [trav_off[t], trav_off[t + 1]) (trav_off[n_traces + 1], may be NULL); cap 0
+ * with dst NULL only sizes the call.  On a multi-device engine the members'
+ * records are joined in the batch's trace order (segment and the shape indices
+ * are trace-relative: nothing is rebased).  otm_traversals_device: the dense
+ * device arrays of a one-device engine (valid until its next batch), ordered
+ * behind the engine's stream.  OTM_EINVAL (message in otm_last_error): a NULL
+ * engine, a size or fetch call with the switch off or with no binary-level
+ * batch with it on as the handle's last batch, cap
+ * below the record count, otm_traversals_device on a multi-device handle. */
+int otm_set_traversals(otm_engine* eng, int on);
+int otm_traversals_info(const otm_engine* eng, int* on);
+int otm_traversals_size(otm_engine* eng, int64_t* n_traces, int64_t* n);
+int otm_fetch_traversals(otm_engine* eng, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n);
+int otm_traversals_device(otm_engine* eng, const void** recs, const int64_t** trav_off, int64_t* n);
+
 /* Per-segment speed histogram, accumulated on the device by every match
  * call: counts u32[n_segments * nbins], bin = floor(kph / bin_kph) clamped to
  * nbins-1, one count per datastore report.  The buffer is CALLER-owned device

@@ -143,6 +143,20 @@ class MatchedPoint(C.Structure):
 
 PT_MATCHED, PT_COLUMN, PT_NODE, PT_CHAIN_START, PT_ROUTE, PT_ANCHOR, PT_SAME_EDGE = 1, 2, 4, 8, 16, 32, 64
 
+# otm_traversal (include/otmatch.h): 56 bytes, natural alignment
+TRAVERSAL_DTYPE = np.dtype([("edge", "<i4"), ("flags", "<u4"), ("begin_offset", "<f4"), ("end_offset", "<f4"),
+                            ("enter_time", "<f8"), ("exit_time", "<f8"), ("begin_shape_index", "<i4"),
+                            ("end_shape_index", "<i4"), ("segment", "<i4"), ("pad", "<i4"), ("way_id", "<i8")])
+
+
+class Traversal(C.Structure):
+    _fields_ = [("edge", C.c_int32), ("flags", C.c_uint32), ("begin_offset", C.c_float), ("end_offset", C.c_float),
+                ("enter_time", C.c_double), ("exit_time", C.c_double), ("begin_shape_index", C.c_int32),
+                ("end_shape_index", C.c_int32), ("segment", C.c_int32), ("pad", C.c_int32), ("way_id", C.c_int64)]
+
+
+TV_CHAIN_START, TV_CHAIN_END, TV_FROM_START, TV_TO_END, TV_INTERNAL, TV_SEGMENT_FIRST = 1, 2, 4, 8, 16, 32
+
 SEG_START_VALID, SEG_END_VALID, SEG_INTERNAL, SEG_START_INT, SEG_END_INT = 1, 2, 4, 8, 16
 REP_T1_INT, REP_T0_INT = 1, 2
 REP_T1_INT_MINUS1 = REP_T1_INT
@@ -164,6 +178,11 @@ def _declare(L):
         "otm_points_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "otm_fetch_points": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
         "otm_points_device": (C.c_int, [vp, pp, C.POINTER(i64)]),
+        "otm_set_traversals": (C.c_int, [vp, C.c_int]),
+        "otm_traversals_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "otm_traversals_size": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+        "otm_fetch_traversals": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
+        "otm_traversals_device": (C.c_int, [vp, pp, pp, C.POINTER(i64)]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

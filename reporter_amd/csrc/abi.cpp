@@ -1936,9 +1936,18 @@ void otm_host_free(void* p) {
   if (p) (void)hipHostFree(p);
 }
 
+// Marks the handle's batch in flight as a binary-level one (otm_match_soa, otm_match_compact,
+// otm_match_device): only those write and keep the matched route (rule 7d).  Under E->mu.
+struct BinaryBatch {
+  otm_engine* E;
+  explicit BinaryBatch(otm_engine* e) : E(e) { E->tv_want = true; }
+  ~BinaryBatch() { E->tv_want = false; }
+};
+
 static int otm_match_soa_impl(otm_engine* E, const otm_batch* in, otm_results* out) {
   if (!E || !in || !out) return fail(OTM_EINVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(E->mu);
+  BinaryBatch bb(E);
   std::string err;
   int rc = otm::match_host_fetch(E, in, nullptr, out, &err);
   return rc ? fail(rc, err) : OTM_OK;
@@ -1947,6 +1956,7 @@ static int otm_match_soa_impl(otm_engine* E, const otm_batch* in, otm_results* o
 static int otm_match_compact_impl(otm_engine* E, const otm_batch_compact* in, otm_results* out) {
   if (!E || !in || !out) return fail(OTM_EINVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(E->mu);
+  BinaryBatch bb(E);
   std::string err;
   int rc;
   if (E->members.empty()) {
@@ -1975,6 +1985,7 @@ static int otm_match_device_impl(otm_engine* E, const otm_batch* in, void* strea
   if (!E || !in) return fail(OTM_EINVAL, "bad arguments");
   if (!E->members.empty()) return fail(OTM_EINVAL, "device batches go to a member engine (otm_engine_member)");
   std::lock_guard<std::mutex> lk(E->mu);
+  BinaryBatch bb(E);
   (void)hipSetDevice(E->device);
   otm::DevBatch b;
   b.n_traces = in->n_traces;
@@ -2257,6 +2268,94 @@ int otm_points_device(otm_engine* E, const void** dev, int64_t* n_points) {
   if (E->pts_n < 0) return fail(OTM_EINVAL, "no batch has run with matched points on");
   *dev = E->pts_n ? E->pts.p : nullptr;
   if (n_points) *n_points = E->pts_n;
+  return OTM_OK;
+}
+
+// Matched route (DESIGN.md §3 rule 7d): the per-handle switch and the last batch's records
+static_assert(sizeof(otm_traversal) == 56 && alignof(otm_traversal) == 8, "traversal record");
+
+int otm_set_traversals(otm_engine* E, int on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  std::lock_guard<std::mutex> lk(E->mu);
+  for (otm_engine* m : E->members) {
+    std::lock_guard<std::mutex> ml(m->mu);
+    m->trav_on = on != 0;
+  }
+  E->trav_on = on != 0;
+  return OTM_OK;
+}
+
+int otm_traversals_info(const otm_engine* E, int* on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (on) *on = E->trav_on ? 1 : 0;
+  return OTM_OK;
+}
+
+int otm_traversals_size(otm_engine* E, int64_t* n_traces, int64_t* n) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  try {
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (!E->members.empty()) {
+      if (!E->trav_on) return fail(OTM_EINVAL, "the matched route is off (otm_set_traversals)");
+      if (E->g_tv_n < 0) return fail(OTM_EINVAL, "no batch has run with the matched route on");
+      if (n_traces) *n_traces = (int64_t)E->g_tv_off.size() - 1;
+      if (n) *n = E->g_tv_n;
+      return OTM_OK;
+    }
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    std::string err;
+    const int rc = otm::engine_traversals_dense(E, &err);
+    if (rc) return fail(rc, err);
+    if (n_traces) *n_traces = E->tv_T;
+    if (n) *n = E->tv_n;
+    return OTM_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+}
+
+static int otm_fetch_traversals_impl(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "matched route: dst is NULL with cap != 0");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (!E->members.empty()) {
+    // the members' records of the group's last batch, joined in trace order (group.cpp)
+    if (!E->trav_on) return fail(OTM_EINVAL, "the matched route is off (otm_set_traversals)");
+    if (E->g_tv_n < 0) return fail(OTM_EINVAL, "no batch has run with the matched route on");
+    if (n) *n = E->g_tv_n;
+    if (trav_off) std::memcpy(trav_off, E->g_tv_off.data(), E->g_tv_off.size() * sizeof(int64_t));
+    if (!dst && cap == 0) return OTM_OK;
+    if (cap < E->g_tv_n) return fail(OTM_EINVAL, "matched route: cap below the batch's record count");
+    if (E->g_tv_n) std::memcpy(dst, E->g_tv.data(), (size_t)E->g_tv_n * sizeof(otm_traversal));
+    return OTM_OK;
+  }
+  if (E->device >= 0) (void)hipSetDevice(E->device);
+  std::string err;
+  int rc = otm::engine_fetch_traversals(E, dst, cap, trav_off, n, &err);
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n) {
+  try {
+    return otm_fetch_traversals_impl(E, dst, cap, trav_off, n);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  } catch (const std::exception& e) {
+    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
+  }
+}
+
+int otm_traversals_device(otm_engine* E, const void** recs, const int64_t** trav_off, int64_t* n) {
+  if (!E || !recs) return fail(OTM_EINVAL, "engine or recs is NULL");
+  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (E->device >= 0) (void)hipSetDevice(E->device);
+  std::string err;
+  const int rc = otm::engine_traversals_dense(E, &err);
+  if (rc) return fail(rc, err);
+  *recs = E->tv_n ? E->tv_dense.p : nullptr;
+  if (trav_off) *trav_off = E->tv_off.p;
+  if (n) *n = E->tv_n;
   return OTM_OK;
 }
 

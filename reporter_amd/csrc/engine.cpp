@@ -353,6 +353,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->trans_lanes = P->trans_lanes;
   C->queue_kph = P->queue_kph;
   C->points_on = P->points_on;
+  C->trav_on = P->trav_on;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -753,6 +754,13 @@ static int bind_out(otm_engine* E, int32_t NT, int64_t NP, DevOut& o, std::strin
   return OTM_OK;
 }
 
+// The matched route's regions and counts (rule 7d), in DevOut's region layout.
+static int bind_trav(otm_engine* E, int32_t NT, int64_t NP, DevTrav& tv, std::string* err) {
+  TRY(bind_buf(tv.rec, E->tv_rec, out_region_cap(E, NP), err));
+  TRY(bind_buf(tv.cnt, E->tv_cnt, (size_t)NT + 1, err));
+  return OTM_OK;
+}
+
 // One attempt at a batch, enqueued with no host synchronisation: buffers are
 // sized from capacities (transition matrices, path pool) that the kernels
 // check; an overflow sets w.abort, every later kernel returns at once, and
@@ -764,6 +772,10 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
                              int from = RESUME_ALL) {
   const int64_t NP = b.n_points;
   const int32_t NT = b.n_traces;
+  // (any batch overwrites what the last one's matched route was made from: nothing of it stays fetchable,
+  // whatever becomes of this one)
+  E->tv_T = -1;
+  E->tv_n = -1;
   DevWork w{};
   TRY(bind_point_work(E, NP, NT, w, err));
 
@@ -842,6 +854,15 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     TRY(E->pts.ensure((size_t)NP + 1, err));
     launch_points(E->g, b, dp, w, E->pts.p, s);
     E->pts_n = NP;
+  }
+  // K7d (DESIGN.md §3 rule 7d): likewise, and only for a binary-level batch.  Every attempt writes
+  // each trace's whole count and region; the dense form is made at the first fetch.
+  if (E->trav_on && E->tv_want) {
+    DevTrav tv{};
+    TRY(bind_trav(E, NT, NP, tv, err));
+    HIPCHK(hipMemsetAsync(tv.cnt + NT, 0, sizeof *tv.cnt, s));
+    launch_traversals(E->g, b, w, o, tv, s);
+    E->tv_T = NT;
   }
   launch_report(b, E->drc, w, o, s, mk);
   HIPCHK(hipGetLastError());
@@ -1587,6 +1608,55 @@ int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int6
   HIPCHK(big_copy(E->h_pts.p, E->pts.p, bytes, hipMemcpyDeviceToHost, E->stream));
   HIPCHK(wait_batch(E, E->stream, E->pts_n));
   std::memcpy(dst, E->h_pts.p, bytes);
+  return OTM_OK;
+}
+
+int engine_traversals_dense(otm_engine* E, std::string* err) {
+  if (!E->trav_on) {
+    *err = "the matched route is off (otm_set_traversals)";
+    return OTM_EINVAL;
+  }
+  if (E->tv_T < 0) {
+    *err = "no batch has run with the matched route on";
+    return OTM_EINVAL;
+  }
+  if (E->tv_n >= 0) return OTM_OK;  // made by an earlier call for this batch
+  hipStream_t s = E->stream;
+  const int32_t NT = E->tv_T;
+  // dense offsets: the exclusive scan of the per-trace counts, then one copy
+  // pass out of the per-trace regions
+  TRY(E->tv_off.ensure((size_t)NT + 1, err));
+  TRY(E->h_tv_off.ensure((size_t)NT + 1, err));
+  HIPCHK(hipMemcpyAsync(E->tv_off.p, E->tv_cnt.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToDevice, s));
+  if (NT) scan_i64(E->tv_off.p, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+  HIPCHK(hipMemcpyAsync(E->h_tv_off.p, E->tv_off.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(wait_batch(E, s, E->last_P));
+  const int64_t n = E->h_tv_off.p[NT];
+  TRY(E->tv_dense.ensure((size_t)n + 1, err));
+  if (NT && n) {
+    launch_trav_compact(NT, E->seg_ub.p, E->tv_off.p, E->tv_rec.p, E->tv_dense.p, s);
+    HIPCHK(hipGetLastError());
+  }
+  E->tv_n = n;
+  return OTM_OK;
+}
+
+int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
+                            std::string* err) {
+  TRY(engine_traversals_dense(E, err));
+  if (n) *n = E->tv_n;
+  if (trav_off) std::memcpy(trav_off, E->h_tv_off.p, ((size_t)E->tv_T + 1) * 8);
+  if (!dst && cap == 0) return OTM_OK;  // sizing call
+  if (!dst || cap < E->tv_n) {
+    *err = "matched route: cap below the batch's record count";
+    return OTM_EINVAL;
+  }
+  const size_t bytes = (size_t)E->tv_n * sizeof(otm_traversal);
+  if (!bytes) return OTM_OK;
+  TRY(E->h_tv.ensure((size_t)E->tv_n, err));
+  HIPCHK(big_copy(E->h_tv.p, E->tv_dense.p, bytes, hipMemcpyDeviceToHost, E->stream));
+  HIPCHK(wait_batch(E, E->stream, E->tv_n));
+  std::memcpy(dst, E->h_tv.p, bytes);
   return OTM_OK;
 }
 

@@ -290,6 +290,23 @@ struct otm_engine {
   otm::DevBuf<otm_matched_point> pts;
   otm::PinBuf<otm_matched_point> h_pts;
   std::vector<otm_matched_point> g_pts;
+  // matched route (otm_set_traversals, DESIGN.md §3 rule 7d): off, a batch launches and allocates
+  // nothing for it; on, only a binary-level batch does (a JSON, request or batcher batch on the handle
+  // writes none and leaves none to fetch).  tv_rec / tv_cnt: DevTrav's regions and counts of the last
+  // such batch (tv_T its trace count, -1: none); tv_off / tv_dense: the counts' scan and the dense
+  // records, made at the first fetch or device call (tv_n their number, -1: not made yet); h_tv /
+  // h_tv_off: the pinned staging of otm_fetch_traversals; g_tv / g_tv_off: a multi-device engine's
+  // joined records and offsets (g_tv_n their number, -1: none)
+  bool trav_on = false;
+  bool tv_want = false;  // the batch in flight is a binary-level one (abi.cpp BinaryBatch): only those keep records
+  int32_t tv_T = -1;
+  int64_t tv_n = -1, g_tv_n = -1;
+  otm::DevBuf<otm_traversal> tv_rec, tv_dense;
+  otm::DevBuf<int64_t> tv_cnt, tv_off;
+  otm::PinBuf<otm_traversal> h_tv;
+  otm::PinBuf<int64_t> h_tv_off;
+  std::vector<otm_traversal> g_tv;
+  std::vector<int64_t> g_tv_off;
 };
 
 namespace otm {
@@ -352,6 +369,14 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
 // the last batch's matched points (E->pts_n of them) copied to dst; OTM_EINVAL
 // when the switch is off, no batch ran with it on, or cap is below the count
 int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err);
+// the last batch's matched route: compacts the regions on the device (once per
+// batch; E->tv_dense, E->tv_off, E->tv_n); OTM_EINVAL when the switch is off or
+// no batch ran with it on
+int engine_traversals_dense(otm_engine* E, std::string* err);
+// ... and copies the dense records to dst[cap] and the tv_T + 1 offsets to
+// trav_off (may be null); OTM_EINVAL also when cap is below the count
+int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
+                            std::string* err);
 int engine_counters(otm_engine* E, otm_work_counters* out);
 // report() on the GPU over caller-supplied typed segments (otm_report_segments_device):
 // per trace t its points' times [trace_off[t], trace_off[t+1]) and segments

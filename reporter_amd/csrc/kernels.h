@@ -419,6 +419,13 @@ struct DevOut {
   PairTab pairs;         // the pair window's table (pairs.h); key nullptr: none
 };
 
+// The matched route's arrays (DESIGN.md §3 rule 7d; bound only with the handle's
+// switch on): trace t's records in DevOut's region layout, at seg_base[t].
+struct DevTrav {
+  otm_traversal* rec;  // [] regions (capacity = DevOut's bound total)
+  int64_t* cnt;        // [T+1] records per trace (cnt[T] = 0: scanned into trav_off at the fetch)
+};
+
 // Per-kernel timing (otm_get_kernel_ms): when ev != nullptr the launchers
 // record ev[2k] just before and ev[2k+1] just after kernel k, on the launch
 // stream.  Order and names: kKernelNames in kernels.hip.
@@ -481,6 +488,13 @@ void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream
 // only with the handle's switch on; no timing slot of its own
 void launch_points(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, otm_matched_point* out,
                    hipStream_t s);
+// K7d: one otm_traversal per traversed edge into trace t's region of tv.rec and
+// their number into tv.cnt[t] (DESIGN.md §3 rule 7d), after launch_segments;
+// launched only with the handle's switch on; no timing slot of its own
+void launch_traversals(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, const DevTrav& tv, hipStream_t s);
+// ... and their fetch-time compaction: off = the exclusive scan of tv.cnt
+void launch_trav_compact(int32_t n_traces, const int64_t* seg_base, const int64_t* off, const otm_traversal* reg,
+                         otm_traversal* dst, hipStream_t s);
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);

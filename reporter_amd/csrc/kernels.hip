@@ -4958,6 +4958,292 @@ __global__ __launch_bounds__(TB) void k_points(DevGraph g, DevBatch b, DevParams
   }
 }
 
+// ============================================================== K7d matched route
+// (after K7c, for the same reason: the code object lays the timed kernels out as it did without it)
+// What SegEmitter::push compares of two consecutive traversals' edges.
+struct TvAttr {
+  int32_t seg, pos;
+  uint32_t fl;
+};
+__device__ __forceinline__ TvAttr tv_attr(const DevGraph& g, int32_t e) {
+  const uint4 r = edge_rec(g, e);
+  return TvAttr{rec_seg(r), rec_pos(r), rec_flags(r)};
+}
+// SegEmitter::push's join test: c behind p, both of one chain
+__device__ __forceinline__ bool tv_join(const TvAttr& p, const TvAttr& c) {
+  if (c.seg >= 0) return p.seg == c.seg && c.pos == p.pos + 1;
+  return p.seg < 0 && ((c.fl ^ p.fl) & SegEmitter<true>::OTM_EDGE_INTERNAL_D) == 0;
+}
+// one record into the trace's region reg[cap] (a slot past the bound is dropped, never written)
+__device__ __forceinline__ void tv_store(otm_traversal* reg, int32_t slot, int32_t cap, int32_t edge, const EAttr& at,
+                                         uint32_t flags, float off0, float off1, double t0, double t1, int sh0, int sh1,
+                                         int grp) {
+  if (slot >= cap) return;
+  otm_traversal r;
+  r.edge = edge;
+  r.flags = flags | (off0 == 0.0f ? OTM_TV_FROM_START : 0u) | (off1 == at.len ? OTM_TV_TO_END : 0u) |
+            (at.seg < 0 && (at.flags & SegEmitter<true>::OTM_EDGE_INTERNAL_D) ? OTM_TV_INTERNAL : 0u);
+  r.begin_offset = off0;
+  r.end_offset = off1;
+  r.enter_time = t0;
+  r.exit_time = t1;
+  r.begin_shape_index = sh0;
+  r.end_shape_index = sh1;
+  r.segment = grp;
+  r.pad = 0;
+  r.way_id = at.way;
+  reg[slot] = r;
+}
+
+// One wavefront per trace, lanes over its points in chunks of 64, plus one
+// virtual point behind the last (segments_trace's p == n): rule 7d's records,
+// the Trav values segments_trace hands to SegEmitter::push, in that order, into
+// the trace's region at seg_base[t] (k_seg_bound's bound is one on traversals)
+// and their number into cnt[t].  The walk as scans over the wave, every carry
+// going forward so that a trace of any length takes this one form:
+//  * a lane's previous state: an exclusive max-scan of the states' points;
+//  * the open traversal before a lane: the latest opener (a chain start, or a
+//    step that left its edge) -- a max-scan of the openers' lanes, its t0 / sh0 /
+//    off0 read from that lane, or from the carry when it lies in an earlier
+//    chunk; its largest offset: a segmented max-scan of the states' offsets,
+//    the openers its heads;
+//  * a lane emits: a step that leaves its edge the close of the open traversal
+//    (none from a node candidate) and its path edges; a chain start and the
+//    virtual point the final close of the chain before them (>= 2 states, not
+//    at a node) -- so nothing looks ahead; a sum-scan gives the slots;
+//  * `segment` is a sum-scan of group starts: a lane counts the starts inside
+//    its own run, and its first record is tested against the last record of
+//    the latest emitting lane before it (or the carry).
+// Times and shape indices are step_bound's at the walk's x (start, start + dd,
+// the path edges' f32 lengths summed in path order), so they are the bits
+// k_segments used.  OTM_TV_CHAIN_END needs the record after: k_trav_compact
+// sets it.  Every read of a per-point array is of the trace's own points.
+__global__ __launch_bounds__(TB) void k_traversals(DevGraph g, DevBatch b, DevWork w, DevOut o, DevTrav tv) {
+  if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
+  const int lane = threadIdx.x;
+  for (int32_t t = blockIdx.x; t < b.n_traces; t += gridDim.x) {
+    const int64_t a = b.trace_off[t];
+    const int n = (int)(b.trace_off[t + 1] - a);
+    const int64_t rb = o.seg_base[t];
+    const int32_t cap = (int32_t)(o.seg_base[t + 1] - rb);
+    otm_traversal* reg = tv.rec + rb;
+    if (w.trace_err[t] != 0) {
+      if (lane == 0) tv.cnt[t] = 0;
+      continue;
+    }
+    // carried from chunk to chunk: the last state's point and whether it began
+    // a chain, the chains begun, the open traversal's fields and largest
+    // offset, the slot and group cursors, the last record's attributes and chain
+    int c_lastp = -1, c_lastcs = 1, c_chain = 0, c_slot = 0, c_grp = 0, c_sh0 = 0, c_pch = -1;
+    double c_t0 = 0.0;
+    float c_off0 = 0.0f, c_max = 0.0f;
+    TvAttr c_pa{-1, 0, 0u};
+    for (int c0 = 0; c0 <= n; c0 += TB) {
+      const int pl = c0 + lane;
+      const bool in = pl < n, virt = pl == n;
+      const int64_t k = a + pl;
+      const bool isst = in && w.is_col[k] != 0 && w.state[k] >= 0;
+      // ---- the previous state, chains
+      int lpi = wave_incl_max(isst ? pl : -1, lane);
+      lpi = lpi > c_lastp ? lpi : c_lastp;
+      int lp = __shfl_up(lpi, 1, 64);
+      if (lane == 0) lp = c_lastp;
+      const bool cs = isst ? (w.chain_start[k] != 0 || lp < 0) : virt;
+      int pcs = __shfl((int)cs, (lp - c0) & 63, 64);  // whether the previous state began its chain
+      if (lp < c0) pcs = c_lastcs;
+      const int ch = c_chain + wave_incl_scan(cs ? 1 : 0, lane);
+      int32_t ei = -1, ej = -1;
+      float oi = 0.0f, oj = 0.0f;
+      if (isst) {
+        const int2 cj = w.chosen[k];
+        ej = cj.x;
+        oj = __int_as_float(cj.y);
+      }
+      if ((isst || virt) && lp >= 0) {
+        const int2 ci = w.chosen[a + lp];
+        ei = ci.x;  // the open traversal's edge
+        oi = __int_as_float(ci.y);
+      }
+      const bool step = isst && !cs;
+      const bool leaves = step && !same_edge_step(ei, oi, ej, oj);
+      const bool opener = isst && (cs || leaves);
+      // ---- a leaving step's route: its length in route order, its first and last
+      // records' attributes and the group starts between them; the re-open on the new edge
+      int nem = 0, plen = 0, poff = 0, inner = 0, my_sh0 = pl;
+      float start = 0.0f, Rd = 0.0f, my_off0 = oj;
+      double ta = 0.0, tb = 0.0, my_t0 = 0.0;
+      bool hasclose = false;
+      TvAttr fa{-1, 0, 0u}, la{-1, 0, 0u};
+      if (isst && cs) my_t0 = b.time[k];
+      if (leaves) {
+        const int32_t pln = w.path_len[k];
+        plen = pln > 0 ? pln : 0;
+        poff = w.path_off[k];
+        Rd = w.route_dist[k];
+        ta = b.time[a + lp];
+        tb = b.time[k];
+        start = src_start(g, ei, oi);
+        hasclose = !cand_node(oi);
+        bool have = hasclose;
+        if (hasclose) fa = la = tv_attr(g, ei);
+        float dd = 0.0f;
+        for (int i = 0; i < plen; ++i) {
+          const uint4 er = edge_rec(g, w.path_pool[poff + i]);
+          const TvAttr c{rec_seg(er), rec_pos(er), rec_flags(er)};
+          dd = dd + rec_len(er);
+          if (!have) fa = c;
+          else if (!tv_join(la, c)) ++inner;
+          have = true;
+          la = c;
+        }
+        int sh;
+        step_bound(b, w, a, lp, pl, Rd, ta, tb, start + dd, my_t0, sh);
+        my_sh0 = sh;
+        my_off0 = 0.0f;
+        nem = (hasclose ? 1 : 0) + plen;
+      }
+      // ---- the open traversal before this lane
+      const int loi = wave_incl_max(opener ? lane : -1, lane);
+      int lox = __shfl_up(loi, 1, 64);
+      if (lane == 0) lox = -1;
+      double x_t0 = __shfl(my_t0, lox & 63, 64);
+      float x_off0 = __shfl(my_off0, lox & 63, 64);
+      int x_sh0 = __shfl(my_sh0, lox & 63, 64);
+      if (lox < 0) {
+        x_t0 = c_t0;
+        x_off0 = c_off0;
+        x_sh0 = c_sh0;
+      }
+      float v = isst ? oj : -1.0f;
+      bool head = opener;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const float vn = __shfl_up(v, d, 64);
+        const int hn = __shfl_up((int)head, d, 64);
+        if (lane >= d) {
+          if (!head) v = vn > v ? vn : v;
+          head = head || hn != 0;
+        }
+      }
+      if (!head) v = c_max > v ? c_max : v;
+      float cmx = __shfl_up(v, 1, 64);  // the open traversal's largest offset before this lane
+      if (lane == 0) cmx = c_max;
+      // ---- the final close of the chain that ends before this lane
+      const bool fin = (isst || virt) && cs && lp >= 0 && !pcs && !cand_node(cmx);
+      if (fin) {
+        fa = la = tv_attr(g, ei);
+        nem = 1;
+      }
+      const int rch = fin ? ch - 1 : ch;  // the chain of this lane's records
+      // ---- slots, the record before, groups
+      const int inc = wave_incl_scan(nem, lane);
+      const int slot = c_slot + inc - nem;
+      const int lei = wave_incl_max(nem > 0 ? lane : -1, lane);
+      int lex = __shfl_up(lei, 1, 64);
+      if (lane == 0) lex = -1;
+      TvAttr pa;
+      pa.seg = __shfl(la.seg, lex & 63, 64);
+      pa.pos = __shfl(la.pos, lex & 63, 64);
+      pa.fl = (uint32_t)__shfl((int)la.fl, lex & 63, 64);
+      int pch = __shfl(rch, lex & 63, 64);
+      if (lex < 0) {
+        pa = c_pa;
+        pch = c_pch;
+      }
+      const bool newchain = nem > 0 && pch != rch;
+      const bool fstart = nem > 0 && (newchain || !tv_join(pa, fa));
+      const int gs = nem > 0 ? inner + (fstart ? 1 : 0) : 0;
+      const int ginc = wave_incl_scan(gs, lane);
+      int gi = c_grp + ginc - gs - 1;  // the group of the record before this lane's first
+      // ---- the carries
+      {
+        const int lo63 = __shfl(loi, 63, 64), le63 = __shfl(lei, 63, 64);
+        const double n_t0 = __shfl(my_t0, lo63 & 63, 64);
+        const float n_off0 = __shfl(my_off0, lo63 & 63, 64);
+        const int n_sh0 = __shfl(my_sh0, lo63 & 63, 64);
+        if (lo63 >= 0) {
+          c_t0 = n_t0;
+          c_off0 = n_off0;
+          c_sh0 = n_sh0;
+        }
+        const int n_seg = __shfl(la.seg, le63 & 63, 64), n_pos = __shfl(la.pos, le63 & 63, 64);
+        const int n_fl = __shfl((int)la.fl, le63 & 63, 64), n_ch = __shfl(rch, le63 & 63, 64);
+        if (le63 >= 0) {
+          c_pa = TvAttr{n_seg, n_pos, (uint32_t)n_fl};
+          c_pch = n_ch;
+        }
+        c_max = __shfl(v, 63, 64);
+        const int np = __shfl(lpi, 63, 64);
+        const int ncs = __shfl((int)cs, (np - c0) & 63, 64);
+        if (np >= c0) c_lastcs = ncs;
+        c_lastp = np;
+        c_chain = __shfl(ch, 63, 64);
+        c_slot += __shfl(inc, 63, 64);
+        c_grp += __shfl(ginc, 63, 64);
+      }
+      // ---- the records
+      if (fin) {
+        gi += fstart ? 1 : 0;
+        tv_store(reg, slot, cap, ei, edge_attr(g, ei), (newchain ? OTM_TV_CHAIN_START : 0u) | (fstart ? OTM_TV_SEGMENT_FIRST : 0u),
+                 x_off0, cmx, x_t0, b.time[a + lp], x_sh0, lp, gi);
+      } else if (leaves) {
+        int s = slot;
+        bool first = true;
+        TvAttr pv = pa;
+        if (hasclose) {
+          const EAttr at = edge_attr(g, ei);
+          double t1;
+          int sh;
+          step_bound(b, w, a, lp, pl, Rd, ta, tb, start, t1, sh);
+          gi += fstart ? 1 : 0;
+          tv_store(reg, s++, cap, ei, at, (newchain ? OTM_TV_CHAIN_START : 0u) | (fstart ? OTM_TV_SEGMENT_FIRST : 0u), x_off0,
+                   at.len, x_t0, t1, x_sh0, sh, gi);
+          pv = TvAttr{at.seg, at.seg_pos, at.flags};
+          first = false;
+        }
+        float dd = 0.0f;
+        for (int i = 0; i < plen; ++i) {
+          const int32_t pe = w.path_pool[poff + i];
+          const EAttr at = edge_attr(g, pe);
+          const TvAttr c{at.seg, at.seg_pos, at.flags};
+          const bool st = first ? fstart : !tv_join(pv, c);
+          const uint32_t fl = (first && newchain ? OTM_TV_CHAIN_START : 0u) | (st ? OTM_TV_SEGMENT_FIRST : 0u);
+          gi += st ? 1 : 0;
+          const float xb = start + dd;
+          dd = dd + at.len;
+          const float xe = start + dd;
+          double t0, t1;
+          int sh0, sh1;
+          step_bound(b, w, a, lp, pl, Rd, ta, tb, xb, t0, sh0);
+          step_bound(b, w, a, lp, pl, Rd, ta, tb, xe, t1, sh1);
+          tv_store(reg, s++, cap, pe, at, fl, 0.0f, at.len, t0, t1, sh0, sh1, gi);
+          pv = c;
+          first = false;
+        }
+      }
+    }
+    if (lane == 0) tv.cnt[t] = c_slot < cap ? c_slot : cap;
+  }
+}
+
+// One wavefront per trace: its records from the region to the dense array at
+// off[t] (off: the exclusive scan of k_traversals' counts), OTM_TV_CHAIN_END set
+// on a record whose successor starts a chain or does not exist.  The region's
+// records stay as they are, so a second compaction gives the same bytes.
+__global__ __launch_bounds__(TB) void k_trav_compact(int32_t n_traces, const int64_t* seg_base, const int64_t* off,
+                                                     const otm_traversal* reg, otm_traversal* dst) {
+  const int lane = threadIdx.x;
+  for (int32_t t = blockIdx.x; t < n_traces; t += gridDim.x) {
+    const int64_t rb = seg_base[t], d = off[t];
+    const int n = (int)(off[t + 1] - d);
+    for (int k = lane; k < n; k += TB) {
+      otm_traversal x = reg[rb + k];
+      if (k + 1 == n || (reg[rb + k + 1].flags & OTM_TV_CHAIN_START)) x.flags |= OTM_TV_CHAIN_END;
+      dst[d + k] = x;
+    }
+  }
+}
+
 int grid_for(int64_t n, int per_block, int cap) {
   int64_t g = (n + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -5221,6 +5507,14 @@ void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream
 void launch_points(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, otm_matched_point* out,
                    hipStream_t s) {
   hipLaunchKernelGGL(k_points, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g, b, p, w, out);
+}
+void launch_traversals(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, const DevTrav& tv, hipStream_t s) {
+  hipLaunchKernelGGL(k_traversals, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g, b, w, o, tv);
+}
+void launch_trav_compact(int32_t n_traces, const int64_t* seg_base, const int64_t* off, const otm_traversal* reg,
+                         otm_traversal* dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_trav_compact, dim3(grid_for(n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, n_traces, seg_base, off,
+                     reg, dst);
 }
 void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* tb, hipStream_t s,
                       const Marks& mk) {

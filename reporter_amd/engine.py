@@ -125,12 +125,14 @@ class Results(object):
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
                  trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, matched_points=False,
-                 **meili):
+                 traversals=False, **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
         with ndev > 1): traces go to member murmur2(uuid) % ndev.
         matched_points: the per-point records of DESIGN.md §3 rule 7c
-        (set_points / points; off: nothing changes)."""
+        (set_points / points; off: nothing changes).
+        traversals: the per-edge records of rule 7d (set_traversals /
+        traversals; off: nothing changes)."""
         L = lib()
         self._tmp = None
         if config_path is None:
@@ -152,6 +154,8 @@ class Engine(object):
         self.devices = devs
         if matched_points:
             self.set_points(True)
+        if traversals:
+            self.set_traversals(True)
 
     def members(self):
         """Member count: ndev of a multi-device engine, else 1."""
@@ -461,6 +465,39 @@ class Engine(object):
         p, n = C.c_void_p(), C.c_int64()
         _check(lib().otm_points_device(self.h, C.byref(p), C.byref(n)))
         return p.value or 0, n.value
+
+    def set_traversals(self, on):
+        """The matched-route switch of this handle (otm_set_traversals; a multi-device
+        engine passes it to every member, a clone inherits it when it is made)."""
+        _check(lib().otm_set_traversals(self.h, 1 if on else 0))
+
+    def traversals_info(self):
+        """Whether the matched route is on (otm_traversals_info)."""
+        on = C.c_int()
+        _check(lib().otm_traversals_info(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def traversals(self):
+        """The matched route of the handle's last binary-level batch
+        (otm_traversals_size, otm_fetch_traversals): (records, trav_off) --
+        _lib.TRAVERSAL_DTYPE records, dense and in trace order, trace t's at
+        [trav_off[t], trav_off[t + 1]).  Both arrays are sized by the library's
+        own counts (a member view: its share of the group's batch)."""
+        nt, n = C.c_int64(), C.c_int64()
+        _check(lib().otm_traversals_size(self.h, C.byref(nt), C.byref(n)))
+        off = np.zeros(nt.value + 1, dtype=np.int64)
+        out = np.zeros(n.value, dtype=_lib.TRAVERSAL_DTYPE)
+        _check(lib().otm_fetch_traversals(self.h, out.ctypes.data if n.value else None, n.value, off.ctypes.data,
+                                          C.byref(n)))
+        return out, off
+
+    def traversals_device(self):
+        """(records pointer, trav_off pointer, count) of the last batch's dense
+        records in this GPU's HBM (otm_traversals_device; a one-device engine's,
+        valid until its next batch)."""
+        p, o, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().otm_traversals_device(self.h, C.byref(p), C.byref(o), C.byref(n)))
+        return p.value or 0, o.value or 0, n.value
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))

@@ -238,6 +238,31 @@ def classify_sequences(T, G, twin, at_outlier=lambda k0, k1: False):
     return c
 
 
+def route_agreement(true_path_off, true_path_edges, records, trav_off):
+    """Edge-level agreement of the matched route (Engine.traversals: records,
+    trav_off) with the driven paths (true_paths: true_path_off, edges), trace
+    by trace: an LCS alignment of the two directed-edge sequences (consecutive
+    repeats of an edge folded: a matched chain break re-enters its edge).
+    -> dict: traces, truth / matched (edges in all), paired (in the alignments),
+    missed = truth - paired, extra = matched - paired, recall = paired / truth,
+    precision = paired / matched (1.0 for an empty denominator), exact (traces
+    whose two sequences are equal), empty (traces without a matched edge)."""
+    edges = np.asarray(records["edge"]) if len(records) else np.zeros(0, np.int32)
+    c = dict(traces=len(true_path_off) - 1, truth=0, matched=0, paired=0, exact=0, empty=0)
+    for t in range(c["traces"]):
+        T = _dedup([int(x) for x in true_path_edges[true_path_off[t]:true_path_off[t + 1]]])
+        G = _dedup([int(x) for x in edges[trav_off[t]:trav_off[t + 1]]])
+        c["truth"] += len(T)
+        c["matched"] += len(G)
+        c["paired"] += len(_lcs_pairs(T, G))
+        c["exact"] += 1 if T == G else 0
+        c["empty"] += 0 if G else 1
+    c["missed"], c["extra"] = c["truth"] - c["paired"], c["matched"] - c["paired"]
+    c["recall"] = c["paired"] / c["truth"] if c["truth"] else 1.0
+    c["precision"] = c["paired"] / c["matched"] if c["matched"] else 1.0
+    return c
+
+
 def _graph_section(graph_path, k, dtype):
     import struct
     raw = np.fromfile(graph_path, dtype=np.uint8)

@@ -17,6 +17,11 @@ their true road (outliers: the probe fell outside the search radius).
 Writes a JSON summary (stdout, or --out).  Test infrastructure: it runs the
 oracle (oracle/pyoracle.py) as the matcher it measures (the GPU path is
 bit-identical to it).
+
+--edges adds the edge-level leg (needs the GPU: the oracle computes no
+traversals): the same batch through the engine with the matched route on
+(DESIGN.md §3 rule 7d), and reporter_amd.synth.route_agreement of its records
+with the driven edge paths -- an LCS alignment per trace, in "edges".
 """
 import argparse
 import json
@@ -43,6 +48,7 @@ def main():
     ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
     ap.add_argument("--cache", default=os.environ.get("OTM_GRAPH_CACHE", "/tmp/otm_graphs"))
     ap.add_argument("--meili", default="", help="k=v,... overrides of the matcher parameters")
+    ap.add_argument("--edges", action="store_true", help="the edge-level leg, on the GPU engine's matched route")
     ap.add_argument("--out")
     a = ap.parse_args()
     cfg = synth.CONFIGS[a.config]
@@ -120,6 +126,13 @@ def main():
            "oracle_seconds": round(t_match, 2), "segment_id_agreement": agr["segment_id_agreement"],
            "sequences_exact": agr["sequences_exact"], "breakdown": agr["breakdown"], "columns": col,
            "trace_ends": ends}
+    if a.edges:
+        from reporter_amd import Engine
+        with Engine(graph_path=gpath, traversals=True, **meili) as eng:
+            res = eng.match({k: b[k] for k in ("trace_off", "lat", "lon", "time", "accuracy")})
+            recs, toff = eng.traversals()
+        assert res.segments.tobytes() == orc["segments"].tobytes(), "engine and oracle disagree on the segments"
+        out["edges"] = synth.route_agreement(poff, pedges, recs, toff)
     js = json.dumps(out, indent=1)
     if a.out:
         with open(a.out, "w") as f:
