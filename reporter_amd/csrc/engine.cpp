@@ -787,6 +787,14 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     dp.order_mask = 0;
     dp.cand_wave_all = 1;
   }
+  // OTM_CAND_CHUNK: the entries of a grid row that k_cand_lane scans before it
+  // inserts their hits, 1..64, the width of a lane's hit mask (read per batch:
+  // the tests put chunk boundaries everywhere with small ones)
+  {
+    const char* ce = std::getenv("OTM_CAND_CHUNK");
+    const int ch = ce ? std::atoi(ce) : 64;
+    dp.cand_chunk = ch < 1 ? 1 : (ch > 64 ? 64 : ch);
+  }
   w.ctr = E->counting ? E->ctr.p : nullptr;
   if (E->counting && from == RESUME_ALL) HIPCHK(hipMemsetAsync(E->ctr.p, 0, sizeof(DevCounters), s));
   // the counters' and abort flag's reset, the spill snapshots and the

@@ -191,6 +191,7 @@ struct DevParams {
   int max_candidates;
   int order_mask;
   int cand_wave_all;  // small batch: every probe to the wave tier (latency, not throughput, bound)
+  int cand_chunk;     // lane tier: entries of a grid row scanned before their hits are inserted (1..64)
 };
 
 struct DevReportCfg {

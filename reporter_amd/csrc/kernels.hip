@@ -87,6 +87,29 @@ __device__ __forceinline__ float seg_sqdist(float alat, float alon, float blat, 
   return px * px + py * py;
 }
 
+// seg_sqdist over an ent_geo word {alat, alon, blat, blon}, the two coordinates
+// of a point as one pair: ll = {lat, lon}, sc = {MPD_F, ls}.  The same
+// operations on the same operands as seg_sqdist (the sums of two products with
+// their terms the other way round, which an IEEE sum does not see), so the same
+// bits; written in pairs so that the lane tier's scan gets v_pk_* instructions
+// without the register shuffles that the vectoriser's own pairing needs.
+typedef float float2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float seg_sqdist_pk(const float4 G, float2_t ll, float2_t sc) {
+  const float2_t a = (float2_t{G.x, G.y} - ll) * sc;  // {ay, ax}
+  const float2_t b = (float2_t{G.z, G.w} - ll) * sc;
+  const float2_t v = b - a;
+  const float2_t vv = v * v;
+  const float l2 = vv.y + vv.x;
+  const float2_t av = a * v;
+  const float dot = av.y + av.x;
+  float t = -dot / l2;
+  t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+  t = l2 > 0.0f ? t : 0.0f;
+  const float2_t p = a + t * v;
+  const float2_t pp = p * p;
+  return pp.y + pp.x;
+}
+
 // (round 4 A/B, not kept: a division-free early out in the lane tier's scan
 // for segments whose whole line lies beyond the radius measured slower --
 // k_cand_lane 0.229 vs 0.221 ms on config 2, 1.89 vs 1.85 on config 4; the
@@ -633,62 +656,104 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
     // each row's entries are one contiguous range
     const unsigned long long cells = (unsigned long long)(r1 - r0 + 1) * (unsigned long long)(c1 - c0 + 1);
     unsigned long long ents = 0;
-    for (int rr = r0; rr <= r1 && !spill; ++rr) {
-      {
-        const size_t rbase = (size_t)rr * (size_t)g.grid_cols;
-        const int64_t q0 = g.cell_off[rbase + c0], q1 = g.cell_off[rbase + c1 + 1];
-        if (CTR) ents += (unsigned long long)(q1 - q0);
-        // CAND_INFL entries' loads in flight per step, inserted in entry order: 2 keeps
-        // the 64-VGPR cap without scratch (0.251 -> 0.246 ms config 2, 3.72 -> 3.66 ms config 4 against 4)
-        for (int64_t q = q0; q < q1 && !spill; q += CAND_INFL) {
-          float sq[CAND_INFL];
-          uint32_t en[CAND_INFL];
+    // one hit into the lane's list: insert, update or spill
+    auto insert = [&](uint32_t ent, float sqd) {
+      const uint32_t e = ent >> 4;
+      // every slot's edge read at once and unconditionally -- slots past
+      // n hold stale words, masked by the select -- so the compiler
+      // emits eight LDS reads and selects, not eight guarded branches
+      // (one LDS round trip per hit instead of up to 8)
+      uint32_t ev[CAND_LANE_CAP];
+#pragma unroll
+      for (int m = 0; m < CAND_LANE_CAP; ++m) ev[m] = E[m * S];
+      int f = -1;
+#pragma unroll
+      for (int m = 0; m < CAND_LANE_CAP; ++m) f = (m < n && (ev[m] >> 4) == e) ? m : f;
+      if (f < 0) {
+        if (n == CAND_LANE_CAP) {
+          spill = true;
+          return;
+        }
+        E[n * S] = ent;
+        Q[n * S] = sqd;
+        ++n;
+      } else {
+        const float qf = Q[f * S];
+        if (sqd < qf || (sqd == qf && (ent & 15u) < (E[f * S] & 15u))) {
+          Q[f * S] = sqd;
+          E[f * S] = ent;
+        }
+      }
+    };
+    const float2_t pll = {lat, lon}, psc = {MPD_F, ls};
+    // (engine.cpp clamps it to 1..64, which this leaves as it is; any other
+    // value lands there too, in scalar operations: 0 would never advance, and
+    // the mask has 64 bits)
+    const uint32_t W = (((uint32_t)P.cand_chunk - 1u) & 63u) + 1u;
+    // Three grid rows at a time, their entry ranges laid end to end as one
+    // index range 0..tot: index i is entry i + qa[0] below e1, i + qa[1] - e1
+    // below e2, i + qa[2] - e2 from there (cell_off is 32 bits wide; the sums wrap and come out
+    // right).  The six offsets are loaded together -- one round trip where a
+    // row at a time took three -- and a lane with short rows does not wait at
+    // each row for the wave's longest one: the wave runs max-over-lanes of the
+    // rows' sum, not the sum over rows of the max.
+    for (int rg = r0; rg <= r1 && !spill; rg += 3) {
+      uint32_t qa[3], qb[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const size_t rbase = (size_t)(rg + j <= r1 ? rg + j : r1) * (size_t)g.grid_cols;
+        qa[j] = g.cell_off[rbase + c0];
+        qb[j] = g.cell_off[rbase + c1 + 1];
+      }
+      const uint32_t e1 = qb[0] - qa[0];
+      const uint32_t e2 = e1 + (rg + 1 <= r1 ? qb[1] - qa[1] : 0u);
+      const uint32_t tot = e2 + (rg + 2 <= r1 ? qb[2] - qa[2] : 0u);
+      // (as sums of differences: two selects and one three-operand add per entry)
+      const uint32_t b2 = qa[2] - e2, d1 = qa[1] - e1 - b2, d0 = qa[0] - (qa[1] - e1);
+      if (CTR) ents += (unsigned long long)tot;
+      auto entry_of = [&](uint32_t i) { return (size_t)(uint32_t)(i + b2 + (i < e2 ? d1 : 0u) + (i < e1 ? d0 : 0u)); };
+      // The range in chunks of at most P.cand_chunk (<= 64) entries, each in
+      // two phases.  Scan: every entry's squared distance, CAND_INFL loads in
+      // flight per step; a hit only sets its bit in the lane's mask -- no
+      // cell_ent load, no LDS, no list work, so no step waits on the one
+      // before.  Drain: the mask's bits in ascending order, one insert each,
+      // which is the order the entries have in their rows and the rows in the
+      // grid.
+      for (uint32_t done = 0, cn; done < tot && !spill; done += cn) {
+        cn = tot - done < W ? tot - done : W;
+        unsigned long long hit = 0ull;
+        for (uint32_t k = 0; k < cn; k += CAND_INFL) {
+          // (past the chunk's end the step's first entry once more, its bit
+          // masked: the step's loads are issued together, behind no branch)
+          float4 G[CAND_INFL];
+#pragma unroll
+          for (int u = 0; u < CAND_INFL; ++u) G[u] = g.ent_geo[entry_of(done + k + (u == 0 || k + u < cn ? u : 0))];
+          __builtin_amdgcn_sched_barrier(0);  // (no arithmetic moved up between the loads)
+          uint32_t bits = 0u;
 #pragma unroll
           for (int u = 0; u < CAND_INFL; ++u) {
-            sq[u] = INFINITY;
-            en[u] = 0;
-            if (q + u < q1) {
-              const float4 G = g.ent_geo[q + u];
-              sq[u] = seg_sqdist(G.x, G.y, G.z, G.w, lat, lon, ls);
-            }
+            const float sq = seg_sqdist_pk(G[u], pll, psc);
+            bits |= ((uint32_t)(u == 0 || k + u < cn) & (uint32_t)(sq <= r2)) << u;
           }
-          // the entry's id only for a hit (~1 in 7 entries): the scattered
-          // load is issued by the lanes that need it, not by every lane
-#pragma unroll
-          for (int u = 0; u < CAND_INFL; ++u)
-            if (sq[u] <= r2) en[u] = g.cell_ent[q + u];
-#pragma unroll
-          for (int u = 0; u < CAND_INFL; ++u) {
-            const float sqd = sq[u];
-            if (spill || !(sqd <= r2)) continue;
-            const uint32_t ent = en[u];
-            const uint32_t e = ent >> 4;
-            // every slot's edge read at once and unconditionally -- slots past
-            // n hold stale words, masked by the select -- so the compiler
-            // emits eight LDS reads and selects, not eight guarded branches
-            // (one LDS round trip per hit instead of up to 8)
-            uint32_t ev[CAND_LANE_CAP];
-#pragma unroll
-            for (int m = 0; m < CAND_LANE_CAP; ++m) ev[m] = E[m * S];
-            int f = -1;
-#pragma unroll
-            for (int m = 0; m < CAND_LANE_CAP; ++m) f = (m < n && (ev[m] >> 4) == e) ? m : f;
-            if (f < 0) {
-              if (n == CAND_LANE_CAP) {
-                spill = true;
-                continue;
-              }
-              E[n * S] = ent;
-              Q[n * S] = sqd;
-              ++n;
-            } else {
-              const float qf = Q[f * S];
-              if (sqd < qf || (sqd == qf && (ent & 15u) < (E[f * S] & 15u))) {
-                Q[f * S] = sqd;
-                E[f * S] = ent;
-              }
-            }
-          }
+          hit |= (unsigned long long)bits << k;
+        }
+        while (hit != 0ull && !spill) {
+          // two hits a step, their four loads issued together (a lone last hit
+          // twice, inserted once): each hit's id and, once more, its distance
+          // -- the same operations on the same floats (no contraction), so
+          // the bits the scan tested.  Half the drain's round trips: config 4,
+          // whose sparse rows are mostly hits, 1,337 -> 1,287 us.
+          const size_t qx = entry_of(done + (uint32_t)(__ffsll(hit) - 1));
+          hit &= hit - 1ull;
+          const bool two = hit != 0ull;
+          const size_t qy = two ? entry_of(done + (uint32_t)(__ffsll(hit) - 1)) : qx;
+          hit &= hit - 1ull;
+          const uint32_t ent0 = g.cell_ent[qx], ent1 = g.cell_ent[qy];
+          const float4 G0 = g.ent_geo[qx], G1 = g.ent_geo[qy];
+          __builtin_amdgcn_sched_barrier(0);
+          const float s0 = seg_sqdist_pk(G0, pll, psc), s1 = seg_sqdist_pk(G1, pll, psc);
+          insert(ent0, s0);
+          if (two && !spill) insert(ent1, s1);
         }
       }
     }
