@@ -210,6 +210,40 @@ int engine_init(otm_engine* E, const char* graph_path, int device, std::string* 
       std::memcpy(&fl2[(size_t)e * 2 + 1], &len[e], 4);
     }
     TRY(up(fl2.data(), fl2.size() * 4, fl2.size() * 4, g.e_fl));
+    // A projection's operands (kernels.h DevGraph::e_proj / s_pt): per edge
+    // {first shape point, last shape point, length bits, out_off[from]}, per
+    // shape point {lat, lon, cum, end} -- the file's floats copied, never
+    // recomputed; end = -1 on every point but an edge's last, there
+    // out_off[to], or -2 when the end node has no outgoing edge (kernels.hip
+    // PT_INNER is the -1) -- so a projection and its node snap take one edge
+    // record and then one 32-byte segment, where they took e_shape_off /
+    // e_len, six SoA loads, e_from / e_to and out_off in turn.  (A projection
+    // tells an edge's last point by its end word; the record's second word
+    // gives the readers that walk a whole edge its segment count.)
+    const int32_t* to = (const int32_t*)E->host.section(OTMG_EDGE_TO);
+    const int32_t* soff = (const int32_t*)E->host.section(OTMG_EDGE_SHAPE_OFF);
+    const int32_t* ooff = (const int32_t*)E->host.section(OTMG_NODE_OUT_OFF);
+    const float* slat = (const float*)E->host.section(OTMG_SHAPE_LAT);
+    const float* slon = (const float*)E->host.section(OTMG_SHAPE_LON);
+    const float* scum = (const float*)E->host.section(OTMG_SHAPE_CUM);
+    const size_t ns = h.sec[OTMG_SHAPE_LAT].bytes / 4;
+    std::vector<int32_t> pt(ns * 4 + 4, -1), pr((size_t)h.n_edges * 4 + 4, 0);
+    for (size_t a = 0; a < ns; ++a) {
+      std::memcpy(&pt[a * 4 + 0], &slat[a], 4);
+      std::memcpy(&pt[a * 4 + 1], &slon[a], 4);
+      std::memcpy(&pt[a * 4 + 2], &scum[a], 4);
+    }
+    for (int32_t e = 0; e < h.n_edges; ++e) {
+      const int32_t last = soff[e + 1] - 1;  // (graph.cpp checked the offsets and the nodes)
+      pt[(size_t)last * 4 + 3] = ooff[to[e] + 1] > ooff[to[e]] ? ooff[to[e]] : -2;
+      int32_t* r = &pr[(size_t)e * 4];
+      r[0] = soff[e];
+      r[1] = last;
+      std::memcpy(&r[2], &len[e], 4);
+      r[3] = ooff[from[e]];
+    }
+    TRY(up(pt.data(), pt.size() * 4, pt.size() * 4, g.s_pt));
+    TRY(up(pr.data(), pr.size() * 4, pr.size() * 4, g.e_proj));
   }
   {
     // The grid index of the candidate search.  The file's cells (meili's

@@ -78,6 +78,16 @@ struct DevGraph {
   // and the way numbers' ids (engine.cpp)
   const uint4* e_rec;
   const int2* e_fl;  // {from node, length bits} per edge: a transition source's row and start in one load
+  // A projection's operands in two dependent trips, three loads (kernels.hip
+  // proj_load; engine.cpp builds both): the edge's projection record {first
+  // shape point, last shape point, length bits, out_off[from]} -- the last
+  // word the start node's representative edge -- then the segment's two shape
+  // points, 32 contiguous bytes of s_pt: {lat, lon, cum, end}, the floats of
+  // s_lat / s_lon / s_cum, and end: -1 on every point but an edge's last,
+  // there the end node's representative edge out_off[to], or -2 when that
+  // node has no outgoing edge
+  const int4* e_proj;
+  const float4* s_pt;
   const int64_t* way_tab;
   int32_t n_nodes, n_edges, n_segments, grid_rows, grid_cols;
   double lat0, lon0, cell;

@@ -118,23 +118,38 @@ __device__ __forceinline__ float seg_sqdist_pk(const float4 G, float2_t ll, floa
 // A projection's inputs (the shape segment's two points and cumulative
 // metres, the edge length and its last shape point), loaded apart from the
 // arithmetic so a caller can issue several projections' loads at once.
+// Two dependent trips, three loads: the edge's projection record, then the
+// segment's two point records, 32 contiguous bytes (DevGraph::e_proj / s_pt,
+// the floats of s_lat / s_lon / s_cum and e_len themselves).  rep_from and
+// end are the node snap's answers, loaded with the operands: the start node's
+// representative edge, and point b's end word -- PT_INNER unless b is its
+// edge's last shape point, there the end node's representative edge, or -2
+// when that node has no outgoing edge.
+constexpr int32_t PT_INNER = -1;  // (engine.cpp writes the same value)
 struct ProjIn {
   float alon, alat, blon, blat, ca, cb, len;
-  int32_t b, last;
+  int32_t rep_from, end;
 };
-__device__ __forceinline__ ProjIn proj_load(const DevGraph& g, int32_t e, int32_t k) {
+__device__ __forceinline__ ProjIn proj_points(const DevGraph& g, const int4 er, int32_t k) {
   ProjIn in;
-  const int32_t a = g.e_shape_off[e] + k, b = a + 1;
-  in.last = g.e_shape_off[e + 1] - 1;
-  in.alon = g.s_lon[a];
-  in.alat = g.s_lat[a];
-  in.blon = g.s_lon[b];
-  in.blat = g.s_lat[b];
-  in.ca = g.s_cum[a];
-  in.cb = g.s_cum[b];
-  in.len = g.e_len[e];
-  in.b = b;
+  const int32_t a = er.x + k;
+  // (a's end word is not needed: twelve bytes, a register less in flight)
+  typedef float float3_t __attribute__((ext_vector_type(3)));
+  const float3_t pa = *(const float3_t*)(g.s_pt + a);
+  const float4 pb = g.s_pt[a + 1];
+  in.alat = pa.x;
+  in.alon = pa.y;
+  in.ca = pa.z;
+  in.blat = pb.x;
+  in.blon = pb.y;
+  in.cb = pb.z;
+  in.end = __float_as_int(pb.w);
+  in.len = __int_as_float(er.z);
+  in.rep_from = er.w;
   return in;
+}
+__device__ __forceinline__ ProjIn proj_load(const DevGraph& g, int32_t e, int32_t k) {
+  return proj_points(g, g.e_proj[e], k);
 }
 __device__ __forceinline__ void proj_calc(const ProjIn& in, float lat, float lon, float ls, float& sqd,
                                           float& off_out, bool& at_end) {
@@ -156,8 +171,35 @@ __device__ __forceinline__ void proj_calc(const ProjIn& in, float lat, float lon
   sqd = px * px + py * py;
   float off = in.ca + t * (in.cb - in.ca);
   off_out = off > in.len ? in.len : off;
-  // clamped to the edge's last shape point: the projection is its end node
-  at_end = t == 1.0f && in.b == in.last;
+  // clamped to the edge's last shape point (b == last: b's end word is not
+  // PT_INNER): the projection is its end node
+  at_end = t == 1.0f && in.end != PT_INNER;
+}
+// node snap of a projection at offset off: the representative
+// (first outgoing) edge of the node it snaps to -- the edge's start node at
+// offset 0, its end node when clamped there and the node has an outgoing
+// edge -- or a negative value.  The node candidate is carried as (that edge,
+// offset 0).
+__device__ __forceinline__ int32_t snap_rep(const ProjIn& in, float off, bool at_end) {
+  return off == 0.0f ? in.rep_from : (at_end ? in.end : -1);
+}
+// The closest projection on the whole of an edge, from its projection record:
+// every shape segment, ties to the lowest (the record's two shape indexes give
+// the segment count, so the edge costs one load before its points).
+__device__ __forceinline__ void project_edge(const DevGraph& g, const int4 er, float lat, float lon, float ls,
+                                             float& bsq, float& boff) {
+  bsq = INFINITY;
+  boff = 0.0f;
+  const int32_t nsh = er.y - er.x;
+  for (int sg = 0; sg < nsh; ++sg) {
+    float sqd, off;
+    bool at_end;
+    proj_calc(proj_points(g, er, sg), lat, lon, ls, sqd, off, at_end);
+    if (sqd < bsq) {
+      bsq = sqd;
+      boff = off;
+    }
+  }
 }
 __device__ __forceinline__ void project(const DevGraph& g, int32_t e, int32_t k, float lat, float lon, float ls,
                                         float& sqd, float& off_out, bool& at_end) {
@@ -168,19 +210,6 @@ __device__ __forceinline__ void project(const DevGraph& g, int32_t e, int32_t k,
   bool at_end;
   project(g, e, k, lat, lon, ls, sqd, off_out, at_end);
 }
-// node snap: the node an edge's best projection snaps to -- its
-// start node at offset 0, its end node when clamped there and the node has an
-// outgoing edge -- or -1.  The node candidate is carried as (the node's first
-// outgoing edge, offset 0).
-__device__ __forceinline__ int32_t snap_node(const DevGraph& g, int32_t e, float off, bool at_end) {
-  if (off == 0.0f) return g.e_from[e];
-  if (at_end) {
-    const int32_t v = g.e_to[e];
-    if (g.out_off[v + 1] > g.out_off[v]) return v;
-  }
-  return -1;
-}
-
 __device__ __forceinline__ float probe_radius(const DevParams& P, float acc) {
   const float a = acc > 0.0f ? acc : P.gps_accuracy;
   const float r = a > P.search_radius ? a : P.search_radius;
@@ -766,7 +795,11 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
     // at the smallest distance.  First every entry's snap, SNAP_B entries'
     // loads issued together (a pure function of the entry: round 6 -- the
     // entry-by-entry walk waited on 3-4 dependent loads per entry); then the
-    // merge in entry order, out of LDS.
+    // merge in entry order, out of LDS.  A step is two dependent trips, three
+    // loads an entry -- the edge's projection record, then the segment's two
+    // point records, which carry both nodes' representative edges (proj_load)
+    // -- where it was four trips and twelve loads through e_shape_off / e_len,
+    // the SoA shape arrays, e_from / e_to and out_off.
     // The pass also keeps each entry's offset (0 for a node candidate) for the
     // output loop.  Its squared distance is not kept: Q already holds it.  Q
     // of an edge entry is seg_sqdist over ent_geo of the entry in E (the scan
@@ -784,40 +817,28 @@ __global__ __launch_bounds__(CAND_TB, OTM_CAND_WAVES) void k_cand_lane(DevGraph 
       if (m0 >= n) continue;
       uint32_t em[SNAP_B];
       ProjIn pin[SNAP_B];
+      // (not kept: the next step's edge records loaded during this one, so
+      // that a step is one trip -- 24 B of scratch at the 64-register cap)
 #pragma unroll
       for (int u = 0; u < SNAP_B; ++u) {
         em[u] = m0 + u < n ? E[(m0 + u) * S] : 0u;
         if (m0 + u < n) pin[u] = proj_load(g, (int32_t)(em[u] >> 4), (int32_t)(em[u] & 15u));
       }
-      int32_t vx[SNAP_B];
-      bool node0[SNAP_B], at_end[SNAP_B];
-      float offv[SNAP_B];
 #pragma unroll
       for (int u = 0; u < SNAP_B; ++u) {
-        vx[u] = 0;
-        node0[u] = at_end[u] = false;
-        offv[u] = 0.0f;
         if (m0 + u < n) {
           float sqd, off;
-          proj_calc(pin[u], lat, lon, ls, sqd, off, at_end[u]);
-          offv[u] = off;
-          node0[u] = off == 0.0f;
-          const int32_t e = (int32_t)(em[u] >> 4);
-          if (node0[u] || at_end[u]) vx[u] = node0[u] ? g.e_from[e] : g.e_to[e];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < SNAP_B; ++u) {
-        // snap_node's rule: the start node at offset 0; the end node when
-        // clamped there and it has an outgoing edge
-        if (node0[u] || at_end[u]) {
-          const int32_t o0 = g.out_off[vx[u]], o1 = g.out_off[vx[u] + 1];
-          if (node0[u] || o1 > o0) {
-            E[(m0 + u) * S] = NODE_ENT | ((uint32_t)o0 << 4);
-            offv[u] = 0.0f;
+          bool at_end;
+          proj_calc(pin[u], lat, lon, ls, sqd, off, at_end);
+          // the node's representative edge came with the operands: nothing
+          // more to load (snap_rep)
+          const int32_t rep = snap_rep(pin[u], off, at_end);
+          if (rep >= 0) {
+            E[(m0 + u) * S] = NODE_ENT | ((uint32_t)rep << 4);
+            off = 0.0f;
           }
+          offr[m0 + u] = off;
         }
-        offr[m0 + u] = offv[u];
       }
     }
     for (int m = 0; m < n; ++m) {
@@ -1041,10 +1062,14 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
           if (cexcl[mid] <= gi) lo = mid;
           else hi = mid - 1;
         }
-        const uint32_t ent = g.cell_ent[cstart[lo] + (gi - cexcl[lo])];
+        // the entry's id and its segment's endpoints by the entry's index, one
+        // trip: seg_sqdist over ent_geo is proj_calc's sqd bit for bit (the
+        // lane tier's snap pass says why), so the scan projects nothing
+        const int64_t q = cstart[lo] + (gi - cexcl[lo]);
+        const uint32_t ent = g.cell_ent[q];
+        const float4 G = g.ent_geo[q];
         const int32_t e = (int32_t)(ent >> 4), k = (int32_t)(ent & 15u);
-        float sqd, off;
-        project(g, e, k, lat, lon, ls, sqd, off);
+        const float sqd = seg_sqdist(G.x, G.y, G.z, G.w, lat, lon, ls);
         if (!(sqd <= r2)) continue;
         uint32_t slot = hash32((uint32_t)e) >> (32 - hlog2);
         bool placed = false;
@@ -1119,14 +1144,15 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
       const int32_t e = (int32_t)(((uint32_t)key) >> 5);
       float sqd, off;
       bool at_end;
-      project(g, e, (int32_t)((key >> 1) & 15ull), lat, lon, ls, sqd, off, at_end);
-      const int32_t v = snap_node(g, e, off, at_end);
+      const ProjIn pin = proj_load(g, e, (int32_t)((key >> 1) & 15ull));
+      proj_calc(pin, lat, lon, ls, sqd, off, at_end);
+      const int32_t v = snap_rep(pin, off, at_end);
       if (v < 0) {
         Mem<BIG>::st(&skey[idx], key | 1ull);
         atomicAdd(&s_count, 1);
       } else {
         Mem<BIG>::st(&skey[idx], (unsigned long long)LAB_NONE);
-        const uint32_t rep = (uint32_t)g.out_off[v];
+        const uint32_t rep = (uint32_t)v;
         uint32_t slot = hash32(rep) >> (32 - hlog2);
         while (true) {
           const uint32_t old = atomicCAS(&hkey[slot], EMPTY, rep);
@@ -4658,26 +4684,21 @@ __device__ float interp_pos(const DevGraph& g, const DevBatch& b, const DevParam
   for (int m = 0; m < npc; ++m) {
     RoutePiece pc;
     const int pk = m - (has0 ? 1 : 0);
+    // the piece's edge record first: its length and its segments in one load
+    const bool mid = !(has0 && m == 0) && pk < plen;
+    const int32_t e = has0 && m == 0 ? ei : (mid ? w.path_pool[poff + pk] : ej);
+    const int4 er = g.e_proj[e];
+    const float len = __int_as_float(er.z);
     if (has0 && m == 0) {
-      pc = RoutePiece{ei, oi, g.e_len[ei], 0.0f};
-    } else if (pk < plen) {
-      const int32_t e = w.path_pool[poff + pk];
-      const float len = g.e_len[e];
+      pc = RoutePiece{e, oi, len, 0.0f};
+    } else if (mid) {
       pc = RoutePiece{e, 0.0f, len, start + dd};
       dd = dd + len;
     } else {
-      pc = RoutePiece{ej, 0.0f, oj, start + dd};
+      pc = RoutePiece{e, 0.0f, oj, start + dd};
     }
-    const int32_t s0 = g.e_shape_off[pc.edge], nsh = g.e_shape_off[pc.edge + 1] - s0 - 1;
-    float bsq = INFINITY, boff = 0.0f;
-    for (int sg = 0; sg < nsh; ++sg) {
-      float sqd, off;
-      project(g, pc.edge, sg, lat, lon, ls, sqd, off);
-      if (sqd < bsq) {
-        bsq = sqd;
-        boff = off;
-      }
-    }
+    float bsq, boff;
+    project_edge(g, er, lat, lon, ls, bsq, boff);
     if (!(boff >= pc.o0 && boff <= pc.o1)) continue;
     const float pos = pc.xs + (boff - pc.o0);
     const float cost = bsq / ds + fabsf(pos - gcd) / P.beta;
@@ -4852,26 +4873,20 @@ __device__ int2 interp_foot(const DevGraph& g, const DevBatch& b, const DevParam
   for (int m = 0; m < npc; ++m) {
     RoutePiece pc;
     const int pk = m - (has0 ? 1 : 0);
+    const bool mid = !(has0 && m == 0) && pk < plen;
+    const int32_t e = has0 && m == 0 ? ei : (mid ? w.path_pool[poff + pk] : ej);
+    const int4 er = g.e_proj[e];
+    const float len = __int_as_float(er.z);
     if (has0 && m == 0) {
-      pc = RoutePiece{ei, oi, g.e_len[ei], 0.0f};
-    } else if (pk < plen) {
-      const int32_t e = w.path_pool[poff + pk];
-      const float len = g.e_len[e];
+      pc = RoutePiece{e, oi, len, 0.0f};
+    } else if (mid) {
       pc = RoutePiece{e, 0.0f, len, start + dd};
       dd = dd + len;
     } else {
-      pc = RoutePiece{ej, 0.0f, oj, start + dd};
+      pc = RoutePiece{e, 0.0f, oj, start + dd};
     }
-    const int32_t s0 = g.e_shape_off[pc.edge], nsh = g.e_shape_off[pc.edge + 1] - s0 - 1;
-    float bsq = INFINITY, boff = 0.0f;
-    for (int sg = 0; sg < nsh; ++sg) {
-      float sqd, off;
-      project(g, pc.edge, sg, lat, lon, ls, sqd, off);
-      if (sqd < bsq) {
-        bsq = sqd;
-        boff = off;
-      }
-    }
+    float bsq, boff;
+    project_edge(g, er, lat, lon, ls, bsq, boff);
     if (!(boff >= pc.o0 && boff <= pc.o1)) continue;
     const float pos = pc.xs + (boff - pc.o0);
     const float cost = bsq / ds + fabsf(pos - gcd) / P.beta;
@@ -4889,16 +4904,8 @@ __device__ int2 interp_foot(const DevGraph& g, const DevBatch& b, const DevParam
 __device__ float edge_foot(const DevGraph& g, const DevBatch& b, int32_t e, int64_t k, float lo, float hi) {
   const float lat = b.lat[k], lon = b.lon[k];
   const float ls = MPD_F * cos_deg(lat);
-  const int32_t nsh = g.e_shape_off[e + 1] - g.e_shape_off[e] - 1;
-  float bsq = INFINITY, boff = 0.0f;
-  for (int sg = 0; sg < nsh; ++sg) {
-    float sqd, off;
-    project(g, e, sg, lat, lon, ls, sqd, off);
-    if (sqd < bsq) {
-      bsq = sqd;
-      boff = off;
-    }
-  }
+  float bsq, boff;
+  project_edge(g, g.e_proj[e], lat, lon, ls, bsq, boff);
   return boff < lo ? lo : (boff > hi ? hi : boff);
 }
 
@@ -5398,8 +5405,14 @@ void launch_candidates(const DevGraph& g, const DevBatch& b, const DevParams& p,
   // probes in a row.  Not kept: the grid sized from the batch, a wave per
   // expected spilled probe (n_points / 64 between 256 and 16384: 15,625 waves
   // at 1M points) -- 37.7 against 36.0 us on config 2, 8.5 against 7.8 on
-  // config 4, profiles/graph_words/kernels.json build "c")
-  if (from < RESUME_CAND_BIG) hipLaunchKernelGGL(k_candidates<false>, dim3(4096), dim3(TB), 0, s, g, b, p, w);
+  // config 4, profiles/graph_words/kernels.json build "c"; and again with the
+  // scan on ent_geo and the snap on the packed records: 2,048 waves 54.8 us,
+  // 8,192 waves 34.2 - 34.5, 4,096 waves 33.8, profiles/proj_records/)
+#ifndef OTM_CAND_WAVE_GRID
+#define OTM_CAND_WAVE_GRID 4096
+#endif
+  if (from < RESUME_CAND_BIG)
+    hipLaunchKernelGGL(k_candidates<false>, dim3(OTM_CAND_WAVE_GRID), dim3(TB), 0, s, g, b, p, w);
   hipLaunchKernelGGL(k_candidates<true>, dim3(CAND_BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
   mk.end(KN_CAND_WAVE, s);
 }
