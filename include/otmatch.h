@@ -474,6 +474,65 @@ int otm_traversals_size(otm_engine* eng, int64_t* n_traces, int64_t* n);
 int otm_fetch_traversals(otm_engine* eng, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n);
 int otm_traversals_device(otm_engine* eng, const void** recs, const int64_t** trav_off, int64_t* n);
 
+/* Match scores (extension, DESIGN.md §3 rule 7e): how sure each matched point
+ * of the last binary-level batch is -- one record per input point, in input
+ * point order, written on the GPU (k_scores) beside the matched points.  The
+ * numbers are min-sum max-marginals of the Viterbi stage's own chain, in its
+ * cost units (not a probability: exp(-margin) is the caller's to form), in f32.
+ * Off by default, per handle: with the switch off a match launches and
+ * allocates nothing more.  A clone inherits its parent's value when it is made;
+ * a multi-device engine passes the call to every member.
+ *   cost        the cost of the best complete path of the point's chain
+ *               through its chosen state
+ *   margin      by how much the best complete path through any other state
+ *               of the column costs more (floored at +0; +inf with
+ *               OTM_SC_ALONE when no other state has a finite one)
+ *   chain_cost  the chain's Viterbi minimum; at the chain's last column cost
+ *               is bit-equal to it
+ *   emission    the chosen state's emission cost
+ *   transition  the cost of the step from the previous column's chosen state
+ *               (0 at a chain's first column); folding a chain's records in
+ *               order as ((em0 + tr1) + em1) + tr2 ... in f32 gives chain_cost
+ *               bit for bit
+ *   alt_edge / alt_offset  the runner-up candidate (the lowest state that
+ *               attains the margin) as the Viterbi stage holds it: on a two-way
+ *               street often the opposite directed edge of the same way
+ *   ncand, state, alt  the column's candidate count, the chosen state and the
+ *               runner-up's state (-1 when alone)
+ * Every other point -- an interpolated point, a column without a state, any
+ * point of a trace answered 500 -- has an all-zero record with flags 0, alt -1
+ * and alt_edge -1.
+ * Only the three binary-level calls write records; any other batch on the
+ * handle, and any failed one, ends the last batch's records: a fetch then
+ * answers OTM_EINVAL, never another batch's records. */
+#define OTM_SC_SCORED 1u       /* the record is scored */
+#define OTM_SC_CHAIN_START 2u  /* first column of its chain */
+#define OTM_SC_CHAIN_END 4u    /* last column of its chain */
+#define OTM_SC_ALONE 8u        /* no other state has a finite through-cost */
+#define OTM_SC_TIE 16u         /* margin == 0 */
+typedef struct otm_point_score { /* 32 bytes */
+  float cost, margin, chain_cost, emission, transition;
+  int32_t alt_edge;
+  float alt_offset;
+  uint8_t flags, ncand;
+  int8_t state, alt;
+} otm_point_score;
+/* otm_set_scores: the switch (on != 0).  otm_scores_info: its value.
+ * otm_fetch_scores answers for the handle's last otm_match_soa,
+ * otm_match_compact or otm_match_device batch, any number of times with the
+ * same bytes: *n_points records into dst[cap]; cap 0 with dst NULL only sizes
+ * the call.  On a multi-device engine the members' records are joined in the
+ * batch's point order.  otm_scores_device: the device buffer of a one-device
+ * engine (valid until its next batch), ordered behind the engine's stream.
+ * OTM_EINVAL (message in otm_last_error): a NULL engine, a fetch with the
+ * switch off or with no binary-level batch with it on as the handle's last
+ * batch, cap below the point count, otm_scores_device on a multi-device
+ * handle. */
+int otm_set_scores(otm_engine* eng, int on);
+int otm_scores_info(const otm_engine* eng, int* on);
+int otm_fetch_scores(otm_engine* eng, otm_point_score* dst, int64_t cap, int64_t* n_points);
+int otm_scores_device(otm_engine* eng, const void** dev, int64_t* n_points);
+
 /* Per-segment speed histogram, accumulated on the device by every match
  * call: counts u32[n_segments * nbins], bin = floor(kph / bin_kph) clamped to
  * nbins-1, one count per datastore report.  The buffer is CALLER-owned device

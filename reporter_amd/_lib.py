@@ -157,6 +157,20 @@ class Traversal(C.Structure):
 
 TV_CHAIN_START, TV_CHAIN_END, TV_FROM_START, TV_TO_END, TV_INTERNAL, TV_SEGMENT_FIRST = 1, 2, 4, 8, 16, 32
 
+# otm_point_score (include/otmatch.h): 32 bytes, 4-byte alignment
+SCORE_DTYPE = np.dtype([("cost", "<f4"), ("margin", "<f4"), ("chain_cost", "<f4"), ("emission", "<f4"),
+                        ("transition", "<f4"), ("alt_edge", "<i4"), ("alt_offset", "<f4"), ("flags", "u1"),
+                        ("ncand", "u1"), ("state", "i1"), ("alt", "i1")])
+
+
+class PointScore(C.Structure):
+    _fields_ = [("cost", C.c_float), ("margin", C.c_float), ("chain_cost", C.c_float), ("emission", C.c_float),
+                ("transition", C.c_float), ("alt_edge", C.c_int32), ("alt_offset", C.c_float), ("flags", C.c_uint8),
+                ("ncand", C.c_uint8), ("state", C.c_int8), ("alt", C.c_int8)]
+
+
+SC_SCORED, SC_CHAIN_START, SC_CHAIN_END, SC_ALONE, SC_TIE = 1, 2, 4, 8, 16
+
 SEG_START_VALID, SEG_END_VALID, SEG_INTERNAL, SEG_START_INT, SEG_END_INT = 1, 2, 4, 8, 16
 REP_T1_INT, REP_T0_INT = 1, 2
 REP_T1_INT_MINUS1 = REP_T1_INT
@@ -183,6 +197,10 @@ def _declare(L):
         "otm_traversals_size": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "otm_fetch_traversals": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
         "otm_traversals_device": (C.c_int, [vp, pp, pp, C.POINTER(i64)]),
+        "otm_set_scores": (C.c_int, [vp, C.c_int]),
+        "otm_scores_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "otm_fetch_scores": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
+        "otm_scores_device": (C.c_int, [vp, pp, C.POINTER(i64)]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

@@ -1626,8 +1626,21 @@ otm_engine* otm_engine_member(otm_engine* E, int i) {
   return i < (int)E->members.size() ? E->members[(size_t)i] : nullptr;
 }
 
+// A JSON call on a handle ends its last binary-level batch's match scores (rule
+// 7e): a fetch then answers OTM_EINVAL.  engine_match_once does so for every
+// batch that runs in the handle's own buffers; a JSON call may instead run on
+// batch contexts of its own (a split otm_report_batch, abi.cpp
+// report_many_split), which leave the handle's records standing -- the matched
+// route's documented behaviour (otmatch.h), not the one rule 7e promises.
+static void end_scores(otm_engine* E) {
+  std::lock_guard<std::mutex> lk(E->mu);
+  E->sc_n = -1;
+  E->g_sc_n = -1;
+}
+
 static int otm_report_impl(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
   if (!E || !resp || (!req && len)) return fail(OTM_EINVAL, "bad arguments");
+  end_scores(E);
   int code = 0;
   const char* reqs[1] = {req};
   report_many(E, 1, reqs, &len, &code, resp, resp_len);
@@ -1637,6 +1650,7 @@ static int otm_report_impl(otm_engine* E, const char* req, size_t len, char** re
 static int otm_report_batch_impl(otm_engine* E, int n, const char* const* reqs, const size_t* lens, char** resps,
                      size_t* resp_lens, int* codes) {
   if (!E || n < 0) return fail(OTM_EINVAL, "bad arguments");
+  end_scores(E);
   // bodies in a request arena go to HBM straight from it
   std::vector<std::shared_ptr<ReqSlab>> held;
   reqarena::find(n, reqs, lens, &held);
@@ -1687,6 +1701,7 @@ int otm_request_points(const char* req, size_t len, int fast, float* lat, float*
 
 static int otm_match_json_impl(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
   if (!E || !resp || (!req && len)) return fail(OTM_EINVAL, "bad arguments");
+  end_scores(E);
   std::vector<Req> rq(1);
   std::vector<int> codes(1, 0);
   std::vector<std::string> bodies(1);
@@ -2356,6 +2371,67 @@ int otm_traversals_device(otm_engine* E, const void** recs, const int64_t** trav
   *recs = E->tv_n ? E->tv_dense.p : nullptr;
   if (trav_off) *trav_off = E->tv_off.p;
   if (n) *n = E->tv_n;
+  return OTM_OK;
+}
+
+// Match scores (DESIGN.md §3 rule 7e): the per-handle switch and the last batch's records
+static_assert(sizeof(otm_point_score) == 32 && alignof(otm_point_score) == 4, "point score record");
+
+int otm_set_scores(otm_engine* E, int on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  std::lock_guard<std::mutex> lk(E->mu);
+  for (otm_engine* m : E->members) {
+    std::lock_guard<std::mutex> ml(m->mu);
+    m->scores_on = on != 0;
+  }
+  E->scores_on = on != 0;
+  return OTM_OK;
+}
+
+int otm_scores_info(const otm_engine* E, int* on) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (on) *on = E->scores_on ? 1 : 0;
+  return OTM_OK;
+}
+
+static int otm_fetch_scores_impl(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n_points) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "match scores: dst is NULL with cap != 0");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (!E->members.empty()) {
+    // the members' records of the group's last batch, joined in point order (group.cpp)
+    if (!E->scores_on) return fail(OTM_EINVAL, "match scores are off (otm_set_scores)");
+    if (E->g_sc_n < 0) return fail(OTM_EINVAL, "no batch has run with match scores on");
+    if (n_points) *n_points = E->g_sc_n;
+    if (!dst && cap == 0) return OTM_OK;
+    if (cap < E->g_sc_n) return fail(OTM_EINVAL, "match scores: cap below the batch's point count");
+    if (E->g_sc_n) std::memcpy(dst, E->g_sc.data(), (size_t)E->g_sc_n * sizeof(otm_point_score));
+    return OTM_OK;
+  }
+  if (E->device >= 0) (void)hipSetDevice(E->device);
+  std::string err;
+  int rc = otm::engine_fetch_scores(E, dst, cap, n_points, &err);
+  return rc ? fail(rc, err) : OTM_OK;
+}
+
+int otm_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n_points) {
+  try {
+    return otm_fetch_scores_impl(E, dst, cap, n_points);
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  } catch (const std::exception& e) {
+    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
+  }
+}
+
+int otm_scores_device(otm_engine* E, const void** dev, int64_t* n_points) {
+  if (!E || !dev) return fail(OTM_EINVAL, "engine or dev is NULL");
+  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (!E->scores_on) return fail(OTM_EINVAL, "match scores are off (otm_set_scores)");
+  if (E->sc_n < 0) return fail(OTM_EINVAL, "no batch has run with match scores on");
+  *dev = E->sc_n ? E->sc.p : nullptr;
+  if (n_points) *n_points = E->sc_n;
   return OTM_OK;
 }
 

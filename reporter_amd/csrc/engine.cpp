@@ -388,6 +388,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->queue_kph = P->queue_kph;
   C->points_on = P->points_on;
   C->trav_on = P->trav_on;
+  C->scores_on = P->scores_on;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -795,6 +796,17 @@ static int bind_trav(otm_engine* E, int32_t NT, int64_t NP, DevTrav& tv, std::st
   return OTM_OK;
 }
 
+// The match scores' records, alpha scratch and packed-form list (rule 7e).
+static int bind_scores(otm_engine* E, int32_t NT, int64_t NP, DevScores& sc, std::string* err) {
+  const size_t Pn = (size_t)NP + 1;
+  TRY(bind_buf(sc.rec, E->sc, Pn, err));
+  TRY(bind_buf(sc.alpha, E->sc_alpha, Pn * KIN, err));
+  TRY(bind_buf(sc.alpha_x, E->sc_alpha_x, Pn * KX, err));
+  TRY(bind_buf(sc.rej, E->sc_rej, (size_t)NT + 2, err));
+  sc.rej_n = sc.rej + NT + 1;
+  return OTM_OK;
+}
+
 // One attempt at a batch, enqueued with no host synchronisation: buffers are
 // sized from capacities (transition matrices, path pool) that the kernels
 // check; an overflow sets w.abort, every later kernel returns at once, and
@@ -810,6 +822,7 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   // whatever becomes of this one)
   E->tv_T = -1;
   E->tv_n = -1;
+  E->sc_n = -1;  // (likewise the match scores)
   DevWork w{};
   TRY(bind_point_work(E, NP, NT, w, err));
 
@@ -897,6 +910,16 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     launch_points(E->g, b, dp, w, E->pts.p, s);
     E->pts_n = NP;
   }
+  // K7e (DESIGN.md §3 rule 7e): beside K7c, only with the handle's switch on and only for a binary-level
+  // batch; outside the timing marks.  It reads what K3-K5 left, which nothing after K5 writes before the
+  // next batch, and trace_err as route recovery left it (launched after launch_route: K6 can still fail a
+  // trace, whose records are then all zero); every attempt writes the whole array.
+  if (E->scores_on && E->tv_want) {
+    DevScores sc{};
+    TRY(bind_scores(E, NT, NP, sc, err));
+    launch_scores(b, w, sc, s);
+    E->sc_n = NP;
+  }
   // K7d (DESIGN.md §3 rule 7d): likewise, and only for a binary-level batch.  Every attempt writes
   // each trace's whole count and region; the dense form is made at the first fetch.
   if (E->trav_on && E->tv_want) {
@@ -929,6 +952,14 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       if (cand) E->cand_final = 0;
     }
   } oom{E};
+  // a batch that fails leaves no match scores to fetch
+  struct ScoreGuard {
+    otm_engine* E;
+    bool ok = false;
+    ~ScoreGuard() {
+      if (!ok) E->sc_n = -1;
+    }
+  } scg{E};
   int from = RESUME_ALL;
   DevWork grown{};  // (the tiers' tables as a growth below leaves them: the next attempt binds them again)
   E->last_resumes = 0;
@@ -1032,6 +1063,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       for (int q = first[k]; q <= last[k]; ++q) E->stage_ms[k] += E->kernel_ms[q];
     }
   }
+  scg.ok = true;
   return OTM_OK;
 }
 
@@ -1650,6 +1682,30 @@ int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int6
   HIPCHK(big_copy(E->h_pts.p, E->pts.p, bytes, hipMemcpyDeviceToHost, E->stream));
   HIPCHK(wait_batch(E, E->stream, E->pts_n));
   std::memcpy(dst, E->h_pts.p, bytes);
+  return OTM_OK;
+}
+
+int engine_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n, std::string* err) {
+  if (!E->scores_on) {
+    *err = "match scores are off (otm_set_scores)";
+    return OTM_EINVAL;
+  }
+  if (E->sc_n < 0) {
+    *err = "no batch has run with match scores on";
+    return OTM_EINVAL;
+  }
+  if (n) *n = E->sc_n;
+  if (!dst && cap == 0) return OTM_OK;  // sizing call
+  if (!dst || cap < E->sc_n) {
+    *err = "match scores: cap below the batch's point count";
+    return OTM_EINVAL;
+  }
+  const size_t bytes = (size_t)E->sc_n * sizeof(otm_point_score);
+  if (!bytes) return OTM_OK;
+  TRY(E->h_sc.ensure((size_t)E->sc_n, err));
+  HIPCHK(big_copy(E->h_sc.p, E->sc.p, bytes, hipMemcpyDeviceToHost, E->stream));
+  HIPCHK(wait_batch(E, E->stream, E->sc_n));
+  std::memcpy(dst, E->h_sc.p, bytes);
   return OTM_OK;
 }
 

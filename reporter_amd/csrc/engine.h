@@ -307,6 +307,19 @@ struct otm_engine {
   otm::PinBuf<int64_t> h_tv_off;
   std::vector<otm_traversal> g_tv;
   std::vector<int64_t> g_tv_off;
+  // match scores (otm_set_scores, DESIGN.md §3 rule 7e): off, a batch launches and allocates nothing
+  // for them; on, only a binary-level batch does (tv_want), and any other batch, or a failed one, leaves
+  // none to fetch.  sc: otm_point_score[last_P] of the last such batch (sc_n its count, -1: none);
+  // sc_alpha / sc_alpha_x: K7e's alpha scratch in the candidates' layout; sc_rej: the packed form's
+  // list (its count in the last element); h_sc: the pinned staging of otm_fetch_scores; g_sc: a
+  // multi-device engine's joined records (g_sc_n as sc_n)
+  bool scores_on = false;
+  int64_t sc_n = -1, g_sc_n = -1;
+  otm::DevBuf<otm_point_score> sc;
+  otm::DevBuf<float> sc_alpha, sc_alpha_x;
+  otm::DevBuf<int32_t> sc_rej;
+  otm::PinBuf<otm_point_score> h_sc;
+  std::vector<otm_point_score> g_sc;
 };
 
 namespace otm {
@@ -369,6 +382,9 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
 // the last batch's matched points (E->pts_n of them) copied to dst; OTM_EINVAL
 // when the switch is off, no batch ran with it on, or cap is below the count
 int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err);
+// the last batch's match scores (E->sc_n of them) copied to dst; OTM_EINVAL as
+// engine_fetch_points
+int engine_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n, std::string* err);
 // the last batch's matched route: compacts the regions on the device (once per
 // batch; E->tv_dense, E->tv_off, E->tv_n); OTM_EINVAL when the switch is off or
 // no batch ran with it on

@@ -112,6 +112,7 @@ struct MemberOut {
   std::vector<otm_report_rec> reps;
   std::vector<int64_t> ways;
   std::vector<otm_matched_point> pts;  // (with the matched-points switch on)
+  std::vector<otm_point_score> sc;     // (with the match-scores switch on, a binary-level batch)
   std::vector<otm_traversal> tv;       // (with the matched-route switch on) dense records,
   std::vector<int64_t> tv_off;         // member trace i's at [tv_off[i], tv_off[i + 1])
   int rc = 0;
@@ -131,6 +132,7 @@ void run_member(otm_engine* M, MemberOut& o) {
   (void)hipSetDevice(M->device);
   if (M->group) M->points_on = M->group->points_on;  // a group's batch runs with the group handle's switch
   if (M->group) M->trav_on = M->group->trav_on;
+  if (M->group) M->scores_on = M->group->scores_on;
   if (M->group) M->tv_want = M->group->tv_want;
   otm_results r;
   o.rc = engine_match_host(M, &sb, &o.err);
@@ -146,6 +148,11 @@ void run_member(otm_engine* M, MemberOut& o) {
     o.pts.resize((size_t)sb.n_points);
     o.rc = engine_fetch_points(M, o.pts.data(), sb.n_points, &n, &o.err);
   }
+  if (M->scores_on && M->tv_want && !o.rc) {
+    int64_t n = 0;
+    o.sc.resize((size_t)sb.n_points);
+    o.rc = engine_fetch_scores(M, o.sc.data(), sb.n_points, &n, &o.err);
+  }
   if (M->trav_on && M->tv_want && !o.rc) {
     int64_t n = 0;
     o.tv_off.resize((size_t)sb.n_traces + 1);
@@ -159,6 +166,7 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
   const int nd = (int)G->members.size();
   const int32_t nt = b->n_traces;
   G->g_tv_n = -1;  // (any batch of the group ends the last one's matched route)
+  G->g_sc_n = -1;  // (... and match scores)
   const int64_t p0 = nt > 0 ? b->trace_off[0] : 0;
   const int64_t np = nt > 0 ? b->trace_off[nt] - p0 : 0;
   std::vector<MemberOut> mo((size_t)nd);
@@ -252,6 +260,16 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
       std::copy(o.pts.begin() + m0, o.pts.begin() + m1, G->g_pts.begin() + (b->trace_off[t] - p0));
     }
     G->g_pts_n = np;
+  }
+  // the members' match scores, joined in the batch's point order
+  if (G->scores_on && G->tv_want) {
+    G->g_sc.resize((size_t)np);
+    for (int32_t t = 0; t < nt; ++t) {
+      const MemberOut& o = mo[(size_t)mem[(size_t)t]];
+      const int64_t m0 = o.off[(size_t)pos[(size_t)t]], m1 = o.off[(size_t)pos[(size_t)t] + 1];
+      std::copy(o.sc.begin() + m0, o.sc.begin() + m1, G->g_sc.begin() + (b->trace_off[t] - p0));
+    }
+    G->g_sc_n = np;
   }
   // the members' matched routes, joined in the batch's trace order (every field is trace-relative)
   if (G->trav_on && G->tv_want) {

@@ -506,6 +506,23 @@ void launch_traversals(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut&
 // ... and their fetch-time compaction: off = the exclusive scan of tv.cnt
 void launch_trav_compact(int32_t n_traces, const int64_t* seg_base, const int64_t* off, const otm_traversal* reg,
                          otm_traversal* dst, hipStream_t s);
+// K7e: one otm_point_score per input point into sc.rec[n_points] (DESIGN.md §3
+// rule 7e): a forward sweep that recomputes K5's alpha into the engine's
+// scratch (the candidates' layout), a backward sweep that forms the
+// through-costs and writes the records.  It reads what K3-K5 left (trans,
+// trans_off, the emissions, ncand, state, chain_start) and trace_err as route
+// recovery (K6, the last stage to fail a trace) left it, and writes nothing a
+// pipeline kernel reads; launched only with the handle's switch on;
+// no timing slot of its own.  OTM_SCORE_FORM (1: one wave per trace, 4: four
+// traces per wave, one per DPP row) forces a form, as OTM_VIT_FORM does.
+struct DevScores {
+  otm_point_score* rec;  // [P]
+  float* alpha;          // [P*KIN] alpha of the inline candidate slots
+  float* alpha_x;        // [P*KX]  ... of the overflow slots
+  int32_t* rej;          // [T] traces the packed form hands to the general form
+  int32_t* rej_n;        // [1] their count (zeroed by the launch)
+};
+void launch_scores(const DevBatch& b, DevWork& w, const DevScores& sc, hipStream_t s);
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);

@@ -5316,6 +5316,286 @@ __global__ __launch_bounds__(TB) void k_trav_compact(int32_t n_traces, const int
   }
 }
 
+// ============================================================== K7e match scores
+// (after K7d, for the same reason as K7c)
+// DESIGN.md §3 rule 7e: min-sum forward-backward over the chains K5 decoded.
+// One row of G lanes per trace, lane j = state j: G = 64 is the general form
+// (one wave per trace, columns up to KMAX wide, any length), G = 16 the packed
+// form (one trace per DPP row, four per wave; a trace with a scored column
+// wider than 16 or with more than SC_ROW_PTS points goes to `rej`, which the
+// general form drains in list mode).  Two sweeps over the trace's points:
+//  * forward: alpha as K5 formed it -- em at a chain's first column, else
+//    (min_i (alpha_q(i) + T[i][j])) + em -- kept in the row's registers from
+//    column to column and written to the scratch (sc.alpha / sc.alpha_x);
+//  * backward, from the trace's last point: beta of the later column stays in
+//    registers as g(j) = em(j) + beta(j); beta_q(i) = min_j (T[i][j] + g(j));
+//    m = alpha + beta; the minimum over j != s with its lowest index by a row
+//    butterfly; lane 0 of the row writes the record.
+// The minima are exact, so the order of their operands does not matter; each
+// sum is the one rule 7e writes.  Terms are costs (>= +0, +inf included): no
+// NaN arises.  A broadcast of state i is a DPP row_newbcast operand of the add
+// in the packed form and a readlane in the general one; DPP reads of a lane
+// that EXEC has switched off do not return its value, so, as in
+// k_viterbi_row, both sweeps run with every lane enabled under wave-uniform
+// control flow and mask by selects: a lane past a column's count holds +inf.
+// Which columns are scored, and where chains start, is read from trace_err
+// (as K6 left it: the kernel is launched after route recovery), K5's state
+// and chain_start: a linked column's previous scored column is its col_prev,
+// the scored column before it in the trace (k_viterbi links no other).
+// Every load is inside its array: a block's floats at [trans_off[p],
+// trans_off[p] + Kq * Kp), a point's slots below its count.
+constexpr int SC_ROW_PTS = 128;  // packed form: points per trace (a longer trace would idle its wave's other rows)
+template <int G, int I>
+__device__ __forceinline__ float sc_bcast(float v) {
+  if constexpr (G == 16)
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + I, 0xF, 0xF, false));
+  else
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), I));
+}
+// I0 .. I0 + 3 of min_i (bcast_i(x) + tv[i]), guarded wave-uniformly by kmax
+template <int G, int KM, int I0>
+__device__ __forceinline__ void sc_min4(const float x, const float (&tv)[KM], const int kmax, float& best) {
+  if (I0 < kmax) {
+    const float v0 = sc_bcast<G, I0 + 0>(x) + tv[I0 + 0];
+    const float v1 = sc_bcast<G, I0 + 1>(x) + tv[I0 + 1];
+    const float v2 = sc_bcast<G, I0 + 2>(x) + tv[I0 + 2];
+    const float v3 = sc_bcast<G, I0 + 3>(x) + tv[I0 + 3];
+    best = fminf(best, fminf(fminf(v0, v1), fminf(v2, v3)));
+  }
+}
+template <int G, int KM>
+__device__ __forceinline__ float sc_min(const float x, const float (&tv)[KM], const int kmax) {
+  float best = INFINITY;
+  sc_min4<G, KM, 0>(x, tv, kmax, best);
+  sc_min4<G, KM, 4>(x, tv, kmax, best);
+  sc_min4<G, KM, 8>(x, tv, kmax, best);
+  sc_min4<G, KM, 12>(x, tv, kmax, best);
+  if constexpr (KM > 16) {
+    sc_min4<G, KM, 16>(x, tv, kmax, best);
+    sc_min4<G, KM, 20>(x, tv, kmax, best);
+    sc_min4<G, KM, 24>(x, tv, kmax, best);
+    sc_min4<G, KM, 28>(x, tv, kmax, best);
+  }
+  return best;
+}
+__device__ __forceinline__ float* sc_alpha(const DevScores& sc, int64_t p, int j) {
+  return j < KIN ? sc.alpha + p * KIN + j : sc.alpha_x + p * KX + (j - KIN);
+}
+__device__ __forceinline__ void sc_store(otm_point_score* r, float cost, float margin, float chain_cost, float em,
+                                         float tr, int32_t alt_edge, int32_t alt_off_bits, uint32_t tail) {
+  uint4* q = (uint4*)r;
+  q[0] = make_uint4(fbits(cost), fbits(margin), fbits(chain_cost), fbits(em));
+  q[1] = make_uint4(fbits(tr), (uint32_t)alt_edge, (uint32_t)alt_off_bits, tail);
+}
+template <int G>
+__global__ __launch_bounds__(TB) void k_scores(DevBatch b, DevWork w, DevScores sc, const int32_t* list,
+                                               const int32_t* list_n, int32_t* rej, int32_t* rej_n) {
+  constexpr int NT = TB / G, KM = G == 16 ? 16 : KMAX;
+  static_assert(G == 16 || G == 64, "a DPP row or a wave per trace");
+  static_assert(sizeof(otm_point_score) == 32, "two 16-byte stores a record");
+  if (*w.abort) return;  // a capacity was exceeded: the host redoes the batch
+  const int lane = threadIdx.x;
+  const int g = lane / G, j = lane % G, gb = g * G;
+  const unsigned long long rowmask = G == 64 ? ~0ull : 0xFFFFull;
+  const int32_t nwork = list ? *list_n : b.n_traces;
+  for (int32_t tb0 = blockIdx.x * NT; tb0 < nwork; tb0 += gridDim.x * NT) {
+    const int32_t it = tb0 + g;
+    bool act = it < nwork;
+    const int32_t t = act ? (list ? list[it] : it) : 0;
+    int64_t a = 0;
+    int n = 0;
+    if (act) {
+      a = b.trace_off[t];
+      n = (int)(b.trace_off[t + 1] - a);
+    }
+    // ---- the records of the points without a score, row-parallel: every point
+    // of a trace answered 500 -- K5 leaves such a trace without a state when
+    // the error came before it, but route recovery (K6) can fail a trace whose
+    // columns have states -- and, in the others, every point without a state;
+    // the packed form also looks for what it cannot take
+    const bool err = act && w.trace_err[t] != 0;
+    bool wide = false;
+    for (int pl = j; pl < n; pl += G) {
+      const int32_t st = w.state[a + pl];
+      if (err || st < 0)
+        sc_store(sc.rec + a + pl, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, 0, 0xFF000000u);
+      else
+        wide = wide || w.ncand[a + pl] > KM;
+    }
+    if (err) act = false;  // whole: nothing to sweep, nothing for the list
+    if (rej) {
+      const bool out = act && (n > SC_ROW_PTS || ((__ballot(wide) >> gb) & rowmask) != 0ull);
+      if (out) {
+        if (j == 0) rej[atomicAdd(rej_n, 1)] = t;
+        act = false;
+      }
+    }
+    if (!act) n = 0;
+    const int nmax = __builtin_amdgcn_readfirstlane(wave_max_i(n));
+    // A chunk of G points' words, one point a lane, loaded together and handed
+    // to the row by shuffle at each step, so a step's own loads (emissions,
+    // alpha, its block) do not wait for them: scored << 6 | chain start << 7 |
+    // state << 8 | candidates, and the point's block offset.  A point past
+    // the trace's end, of an idle row or without a state has word 0.
+    auto chunk_words = [&](int c0, int& mw, int64_t& to) {
+      const int pl = c0 + j;
+      const int64_t p = a + (pl < n ? pl : 0);
+      const int32_t st = w.state[p];
+      const int32_t nc = w.ncand[p];
+      const uint8_t cs = w.chain_start[p];
+      to = w.trans_off[p];
+      mw = pl < n && st >= 0 ? (nc & 0x3F) | 0x40 | (cs ? 0x80 : 0) | (st << 8) : 0;
+    };
+    auto word_of = [&](int mw, int64_t to, int k, int& mk, int64_t& tk) {
+      mk = __shfl(mw, gb + k, 64);
+      const int lo = __shfl((int)(uint32_t)to, gb + k, 64), hi = __shfl((int)(to >> 32), gb + k, 64);
+      tk = (int64_t)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
+    };
+    // ---- forward: alpha into the scratch
+    {
+      float prev = INFINITY;
+      int lastK = 0;
+      for (int c0 = 0; c0 < nmax; c0 += G) {
+        int mw;
+        int64_t tw;
+        chunk_words(c0, mw, tw);
+        const int kend = nmax - c0 < G ? nmax - c0 : G;
+        for (int k = 0; k < kend; ++k) {
+          int mk;
+          int64_t to;
+          word_of(mw, tw, k, mk, to);
+          const bool col = (mk & 0x40) != 0;
+          if (__ballot(col) == 0ull) continue;
+          const int64_t p = a + (col ? c0 + k : 0);
+          const int Kp = col ? mk & 0x3F : 0;
+          const bool link = col && !(mk & 0x80);
+          const float emv = cemis(w, p, j < Kp ? j : 0);  // (slot 0 of a point is always there)
+          const float em = j < Kp ? emv : INFINITY;
+          const int Kq = link ? lastK : 0;
+          const int kmax = __builtin_amdgcn_readfirstlane(wave_max_i(Kq));
+          // the block's column j, every load issued before the first is used: a
+          // lane or source outside the block reads the allocation's first float
+          // instead (always there) and drops it
+          const bool inb = link && j < Kp;
+          const float* const tp = w.trans + (inb ? to + j : 0);
+          const int ts = inb ? Kp : 0;
+          float tv[KM];
+#pragma unroll
+          for (int i = 0; i < KM; ++i) tv[i] = INFINITY;
+#pragma unroll
+          for (int i = 0; i < KM; ++i)
+            if (i < kmax) tv[i] = tp[(i < Kq ? i : 0) * ts];
+#pragma unroll
+          for (int i = 0; i < KM; ++i)
+            if (i < kmax) tv[i] = inb && i < Kq ? tv[i] : INFINITY;
+          const float best = sc_min<G, KM>(prev, tv, kmax);
+          const float cur = link ? best + em : em;
+          if (j < Kp) *sc_alpha(sc, p, j) = cur;
+          prev = col ? cur : prev;
+          lastK = col ? Kp : lastK;
+        }
+      }
+    }
+    // ---- backward: beta, the through-costs, the records.  A record's second
+    // half holds the step's own cost T[state[q]][s], which needs the earlier
+    // column's state: lane 0 keeps that half until the walk reaches q.
+    {
+      float g2 = INFINITY;  // em + beta of the later column of the chain
+      int K2 = 0, s2 = 0;
+      int64_t to2 = 0, p2 = 0;
+      bool have = false;    // a later column links to the one at hand
+      float ccost = 0.0f;
+      int2 alt2 = make_int2(-1, 0);
+      uint32_t tail2 = 0;
+      for (int c0 = ((nmax - 1) / G) * G; c0 >= 0 && nmax > 0; c0 -= G) {
+        int mw;
+        int64_t tw;
+        chunk_words(c0, mw, tw);
+        const int kend = nmax - c0 < G ? nmax - c0 : G;
+        for (int k = kend - 1; k >= 0; --k) {
+          int mk;
+          int64_t to;
+          word_of(mw, tw, k, mk, to);
+          const bool col = (mk & 0x40) != 0;
+          if (__ballot(col) == 0ull) continue;
+          const int64_t p = a + (col ? c0 + k : 0);
+          const int st = (mk >> 8) & 0xFF;
+          const int Kp = col ? mk & 0x3F : 0;
+          const bool cs = col && (mk & 0x80);
+          const float emv = cemis(w, p, j < Kp ? j : 0), alv = *sc_alpha(sc, p, j < Kp ? j : 0);
+          const float em = j < Kp ? emv : INFINITY;
+          const float al = j < Kp ? alv : INFINITY;
+          const bool lk = col && have;
+          const int K2L = lk ? K2 : 0;
+          // the later column's record, whole now: its step came from this column's state
+          if (lk && j == 0) {
+            const float tr = w.trans[to2 + (int64_t)st * K2L + s2];
+            ((uint4*)(sc.rec + p2))[1] = make_uint4(fbits(tr), (uint32_t)alt2.x, (uint32_t)alt2.y, tail2);
+          }
+          const int kmax = __builtin_amdgcn_readfirstlane(wave_max_i(K2L));
+          // the later column's block, row j (loads as in the forward sweep)
+          const bool inb = lk && j < Kp;
+          const float* const tp = w.trans + (inb ? to2 + (int64_t)j * K2L : 0);
+          float tv[KM];
+#pragma unroll
+          for (int i = 0; i < KM; ++i) tv[i] = INFINITY;
+#pragma unroll
+          for (int i = 0; i < KM; ++i)
+            if (i < kmax) tv[i] = tp[inb && i < K2L ? i : 0];
+#pragma unroll
+          for (int i = 0; i < KM; ++i)
+            if (i < kmax) tv[i] = inb && i < K2L ? tv[i] : INFINITY;
+          const float bmin = sc_min<G, KM>(g2, tv, kmax);
+          const float beta = lk ? bmin : 0.0f;
+          const bool end = col && !have;
+          const float m = al + beta;  // (+inf past Kp: al is)
+          // a chain's cost: Viterbi's own minimum, at its last column
+          float cc = al;
+#pragma unroll
+          for (int o = G / 2; o > 0; o >>= 1) cc = fminf(cc, __shfl_xor(cc, o, G));
+          ccost = end ? cc : ccost;
+          const float ms = __shfl(m, gb + (col ? st : 0), 64);
+          const float ems = __shfl(em, gb + (col ? st : 0), 64);
+          // the runner-up: (value, state) minimum over j != s, ties to the lower state
+          float bv = col && j < Kp && j != st ? m : INFINITY;
+          int bi = j;
+#pragma unroll
+          for (int o = G / 2; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, G);
+            const int oi = __shfl_xor(bi, o, G);
+            if (ov < bv || (ov == bv && oi < bi)) {
+              bv = ov;
+              bi = oi;
+            }
+          }
+          if (col && j == 0) {
+            const bool alone = !(bv < INFINITY);
+            const float d = bv - ms;
+            const float margin = alone ? INFINITY : (d > 0.0f ? d : 0.0f);
+            alt2 = alone ? make_int2(-1, 0) : crec(w, p, bi);
+            const uint32_t fl = OTM_SC_SCORED | (cs ? OTM_SC_CHAIN_START : 0u) | (end ? OTM_SC_CHAIN_END : 0u) |
+                                (alone ? OTM_SC_ALONE : 0u) | (margin == 0.0f ? OTM_SC_TIE : 0u);
+            tail2 = fl | ((uint32_t)Kp << 8) | ((uint32_t)(st & 0xFF) << 16) |
+                    ((uint32_t)((alone ? -1 : bi) & 0xFF) << 24);
+            uint4* q = (uint4*)(sc.rec + p);
+            q[0] = make_uint4(fbits(ms), fbits(margin), fbits(ccost), fbits(ems));
+            // a chain's first column has no step of its own
+            if (cs) q[1] = make_uint4(0u, (uint32_t)alt2.x, (uint32_t)alt2.y, tail2);
+          }
+          g2 = col ? em + beta : g2;
+          K2 = col ? Kp : K2;
+          s2 = col ? st : s2;
+          to2 = col ? to : to2;
+          p2 = col ? p : p2;
+          have = col ? !cs : have;
+        }
+      }
+      // (K5 starts every chain with a chain start: no half is left over; were one, its step cost is 0)
+      if (have && j == 0) ((uint4*)(sc.rec + p2))[1] = make_uint4(0u, (uint32_t)alt2.x, (uint32_t)alt2.y, tail2);
+    }
+  }
+}
+
 int grid_for(int64_t n, int per_block, int cap) {
   int64_t g = (n + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -5585,6 +5865,32 @@ void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream
 void launch_points(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, otm_matched_point* out,
                    hipStream_t s) {
   hipLaunchKernelGGL(k_points, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g, b, p, w, out);
+}
+void launch_scores(const DevBatch& b, DevWork& w, const DevScores& sc, hipStream_t s) {
+  if (b.n_traces <= 0 || b.n_points <= 0) return;
+  // the form: OTM_SCORE_FORM (1: the general form, 4: the packed form) for the
+  // tests; by default the packed form from the batch size at which
+  // launch_viterbi takes its row form (below it a batch's waves all fit the
+  // GPU at once and four traces a wave only lengthen the one round)
+  // (read per batch: tests switch them)
+  const char* fe = std::getenv("OTM_SCORE_FORM");
+  const int forced = fe ? std::atoi(fe) : 0;
+  constexpr int rmin = 4096;
+  const int form = forced == 1 || forced == 4 ? forced : (b.n_traces >= rmin ? 4 : 1);
+  if (form == 1) {
+    hipLaunchKernelGGL(k_scores<64>, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w, sc,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    return;
+  }
+  // the packed form over every trace; what it cannot take (more than
+  // SC_ROW_PTS points, a scored column wider than 16 candidates) to the
+  // general form through sc.rej (sized for every trace: a block whose list
+  // entries ran out exits at once)
+  (void)hipMemsetAsync(sc.rej_n, 0, sizeof *sc.rej_n, s);
+  hipLaunchKernelGGL(k_scores<16>, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w, sc,
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, sc.rej, sc.rej_n);
+  hipLaunchKernelGGL(k_scores<64>, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w, sc,
+                     (const int32_t*)sc.rej, (const int32_t*)sc.rej_n, (int32_t*)nullptr, (int32_t*)nullptr);
 }
 void launch_traversals(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, const DevTrav& tv, hipStream_t s) {
   hipLaunchKernelGGL(k_traversals, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g, b, w, o, tv);

@@ -125,14 +125,16 @@ class Results(object):
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
                  trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, matched_points=False,
-                 traversals=False, **meili):
+                 traversals=False, scores=False, **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
         with ndev > 1): traces go to member murmur2(uuid) % ndev.
         matched_points: the per-point records of DESIGN.md §3 rule 7c
         (set_points / points; off: nothing changes).
         traversals: the per-edge records of rule 7d (set_traversals /
-        traversals; off: nothing changes)."""
+        traversals; off: nothing changes).
+        scores: the per-point match scores of rule 7e (set_scores / scores;
+        off: nothing changes)."""
         L = lib()
         self._tmp = None
         if config_path is None:
@@ -156,6 +158,8 @@ class Engine(object):
             self.set_points(True)
         if traversals:
             self.set_traversals(True)
+        if scores:
+            self.set_scores(True)
 
     def members(self):
         """Member count: ndev of a multi-device engine, else 1."""
@@ -498,6 +502,33 @@ class Engine(object):
         p, o, n = C.c_void_p(), C.c_void_p(), C.c_int64()
         _check(lib().otm_traversals_device(self.h, C.byref(p), C.byref(o), C.byref(n)))
         return p.value or 0, o.value or 0, n.value
+
+    def set_scores(self, on):
+        """The match-scores switch of this handle (otm_set_scores; a multi-device
+        engine passes it to every member, a clone inherits it when it is made)."""
+        _check(lib().otm_set_scores(self.h, 1 if on else 0))
+
+    def scores_info(self):
+        """Whether match scores are on (otm_scores_info)."""
+        on = C.c_int()
+        _check(lib().otm_scores_info(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def scores(self):
+        """The last binary-level batch's match scores (otm_fetch_scores): one
+        _lib.SCORE_DTYPE record per input point, in input order."""
+        n = C.c_int64()
+        _check(lib().otm_fetch_scores(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=_lib.SCORE_DTYPE)
+        _check(lib().otm_fetch_scores(self.h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def scores_device(self):
+        """(device pointer, count) of the last batch's records in this GPU's HBM
+        (otm_scores_device; a one-device engine's, valid until its next batch)."""
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().otm_scores_device(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))

@@ -22,6 +22,12 @@ bit-identical to it).
 traversals): the same batch through the engine with the matched route on
 (DESIGN.md §3 rule 7d), and reporter_amd.synth.route_agreement of its records
 with the driven edge paths -- an LCS alignment per trace, in "edges".
+
+--scores adds the match-score leg (needs the GPU too): the same batch with the
+match scores on (DESIGN.md §3 rule 7e); the traces are cut into quartiles of
+their least finite margin and the share of exact traces (classify_sequences
+finds no error) is reported per quartile, beside the share of OTM_SC_TIE
+columns, in "scores".  It sets no threshold.
 """
 import argparse
 import json
@@ -49,6 +55,8 @@ def main():
     ap.add_argument("--cache", default=os.environ.get("OTM_GRAPH_CACHE", "/tmp/otm_graphs"))
     ap.add_argument("--meili", default="", help="k=v,... overrides of the matcher parameters")
     ap.add_argument("--edges", action="store_true", help="the edge-level leg, on the GPU engine's matched route")
+    ap.add_argument("--scores", action="store_true",
+                    help="the match-score leg, on the GPU engine (rule 7e): exact traces by least-margin quartile")
     ap.add_argument("--out")
     a = ap.parse_args()
     cfg = synth.CONFIGS[a.config]
@@ -133,6 +141,36 @@ def main():
             recs, toff = eng.traversals()
         assert res.segments.tobytes() == orc["segments"].tobytes(), "engine and oracle disagree on the segments"
         out["edges"] = synth.route_agreement(poff, pedges, recs, toff)
+    if a.scores:
+        # the traces by quartile of their least finite margin: how the share of exact traces moves with it
+        from reporter_amd import Engine, _lib
+        with Engine(graph_path=gpath, scores=True, **meili) as eng:
+            res = eng.match({k: b[k] for k in ("trace_off", "lat", "lon", "time", "accuracy")})
+            rec = eng.scores()
+        assert res.segments.tobytes() == orc["segments"].tobytes(), "engine and oracle disagree on the segments"
+        scored = (rec["flags"] & _lib.SC_SCORED) != 0
+        exact = np.array([c["paired"] == c["truth"] == c["matched"] for c in per])
+        least = np.full(a.vehicles, np.inf)
+        for t in range(a.vehicles):
+            m = rec["margin"][int(off[t]):int(off[t + 1])][scored[int(off[t]):int(off[t + 1])]]
+            m = m[np.isfinite(m)]
+            if len(m):
+                least[t] = float(m.min())
+        have = np.isfinite(least)
+        cuts = np.quantile(least[have], [0.25, 0.5, 0.75]) if have.any() else np.zeros(3)
+        q = np.searchsorted(cuts, least, side="right")
+        out["scores"] = {
+            "scored_columns": int(scored.sum()),
+            "tie_columns_share": float(((rec["flags"] & _lib.SC_TIE) != 0).sum() / max(int(scored.sum()), 1)),
+            "alone_columns_share": float(((rec["flags"] & _lib.SC_ALONE) != 0).sum() / max(int(scored.sum()), 1)),
+            "traces_without_a_finite_margin": int((~have).sum()),
+            "least_margin_quartile_cuts": [float(x) for x in cuts],
+            "exact_share_by_least_margin_quartile": [
+                {"quartile": k + 1, "traces": int((have & (q == k)).sum()),
+                 "exact_share": float(exact[have & (q == k)].mean()) if (have & (q == k)).any() else None}
+                for k in range(4)],
+            "exact_share_all": float(exact.mean()),
+        }
     js = json.dumps(out, indent=1)
     if a.out:
         with open(a.out, "w") as f:
