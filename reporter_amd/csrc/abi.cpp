@@ -39,6 +39,44 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+// The C ABI's exception boundary: nothing throws across it.  An entry point's
+// body runs as f; an allocation failure becomes OTM_ENOMEM and any other
+// std::exception OTM_EINVAL, the message in otm_last_error.
+template <class F>
+int guarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  } catch (const std::exception& e) {
+    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
+  }
+}
+// ... of the entry points that have only ever answered for an allocation failure
+template <class F>
+int guarded_alloc(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return fail(OTM_ENOMEM, "out of host memory");
+  }
+}
+// ... of the entry points that answer an HTTP code and a body: whatever is
+// thrown becomes a 500 like :239-240, its body allocated without anything that throws
+template <class F>
+int guarded_500(char** resp, size_t* resp_len, F&& f) {
+  try {
+    return f();
+  } catch (...) {
+    static const char kBody[] = "{\"error\":\"internal error\"}";
+    char* b = (char*)std::malloc(sizeof kBody);
+    if (b) std::memcpy(b, kBody, sizeof kBody);
+    if (resp) *resp = b;
+    if (resp_len) *resp_len = b ? sizeof kBody - 1 : 0;
+    return 500;
+  }
+}
+
 // Host threads for the per-request work of a large request batch (JSON
 // parse, point extraction, response writing): the machine's cores, at most 16,
 // and at least 256 requests per thread (OTM_HOST_THREADS / OTM_HOST_CHUNK
@@ -1407,7 +1445,7 @@ static bool read_meili(const Value& cfg, otm::MatchConfig* mc, std::string* err)
 
 int otm_config_meili(const char* cfg_path, otm_meili_params* out) {
   if (!cfg_path || !out) return fail(OTM_EINVAL, "bad arguments");
-  try {
+  return guarded_alloc([&] {
     std::string text, perr;
     if (!read_file(cfg_path, &text)) return fail(OTM_EINVAL, std::string("cannot read config ") + cfg_path);
     Value cfg;
@@ -1424,10 +1462,8 @@ int otm_config_meili(const char* cfg_path, otm_meili_params* out) {
     out->gps_accuracy = mc.gps_accuracy;
     out->turn_penalty_factor = mc.turn_penalty_factor;
     out->max_candidates = mc.max_candidates;
-    return OTM_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  }
+    return (int)OTM_OK;
+  });
 }
 
 // "otm":{"queue_speed_kph": v} (DESIGN.md §3 rule 7b): absent or 0 is off; a
@@ -1452,16 +1488,14 @@ static bool read_queue(const Value& cfg, float* kph, std::string* err) {
 
 int otm_config_queue(const char* cfg_path, float* kph) {
   if (!cfg_path || !kph) return fail(OTM_EINVAL, "bad arguments");
-  try {
+  return guarded_alloc([&] {
     std::string text, perr;
     if (!read_file(cfg_path, &text)) return fail(OTM_EINVAL, std::string("cannot read config ") + cfg_path);
     Value cfg;
     if (!otm::json::parse(text, &cfg, &perr)) return fail(OTM_EINVAL, "config: " + perr);
     if (!read_queue(cfg, kph, &perr)) return fail(OTM_EINVAL, perr);
-    return OTM_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  }
+    return (int)OTM_OK;
+  });
 }
 
 static int otm_engine_create_impl(const char* cfg_path, const int* devices, int ndev, otm_engine** out) {
@@ -1626,21 +1660,17 @@ otm_engine* otm_engine_member(otm_engine* E, int i) {
   return i < (int)E->members.size() ? E->members[(size_t)i] : nullptr;
 }
 
-// A JSON call on a handle ends its last binary-level batch's match scores (rule
-// 7e): a fetch then answers OTM_EINVAL.  engine_match_once does so for every
-// batch that runs in the handle's own buffers; a JSON call may instead run on
-// batch contexts of its own (a split otm_report_batch, abi.cpp
-// report_many_split), which leave the handle's records standing -- the matched
-// route's documented behaviour (otmatch.h), not the one rule 7e promises.
-static void end_scores(otm_engine* E) {
+// A JSON-level call on a handle (REC_OTHER_CALL, engine.h): said before its
+// batches run, which may be on batch contexts of the call's own (a split
+// otm_report_batch, report_many_split) and then begin nothing on the handle.
+static void other_call(otm_engine* E) {
   std::lock_guard<std::mutex> lk(E->mu);
-  E->sc_n = -1;
-  E->g_sc_n = -1;
+  otm::end_records(E, otm::REC_OTHER_CALL);
 }
 
 static int otm_report_impl(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
   if (!E || !resp || (!req && len)) return fail(OTM_EINVAL, "bad arguments");
-  end_scores(E);
+  other_call(E);
   int code = 0;
   const char* reqs[1] = {req};
   report_many(E, 1, reqs, &len, &code, resp, resp_len);
@@ -1650,7 +1680,7 @@ static int otm_report_impl(otm_engine* E, const char* req, size_t len, char** re
 static int otm_report_batch_impl(otm_engine* E, int n, const char* const* reqs, const size_t* lens, char** resps,
                      size_t* resp_lens, int* codes) {
   if (!E || n < 0) return fail(OTM_EINVAL, "bad arguments");
-  end_scores(E);
+  other_call(E);
   // bodies in a request arena go to HBM straight from it
   std::vector<std::shared_ptr<ReqSlab>> held;
   reqarena::find(n, reqs, lens, &held);
@@ -1701,7 +1731,7 @@ int otm_request_points(const char* req, size_t len, int fast, float* lat, float*
 
 static int otm_match_json_impl(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
   if (!E || !resp || (!req && len)) return fail(OTM_EINVAL, "bad arguments");
-  end_scores(E);
+  other_call(E);
   std::vector<Req> rq(1);
   std::vector<int> codes(1, 0);
   std::vector<std::string> bodies(1);
@@ -1952,11 +1982,11 @@ void otm_host_free(void* p) {
 }
 
 // Marks the handle's batch in flight as a binary-level one (otm_match_soa, otm_match_compact,
-// otm_match_device): only those write and keep the matched route (rule 7d).  Under E->mu.
+// otm_match_device): only those write the outputs that RecDesc::binary_only names.  Under E->mu.
 struct BinaryBatch {
   otm_engine* E;
-  explicit BinaryBatch(otm_engine* e) : E(e) { E->tv_want = true; }
-  ~BinaryBatch() { E->tv_want = false; }
+  explicit BinaryBatch(otm_engine* e) : E(e) { E->binary_batch = true; }
+  ~BinaryBatch() { E->binary_batch = false; }
 };
 
 static int otm_match_soa_impl(otm_engine* E, const otm_batch* in, otm_results* out) {
@@ -2225,214 +2255,158 @@ int otm_queue_info(const otm_engine* E, float* kph) {
   return OTM_OK;
 }
 
-// Matched points (DESIGN.md §3 rule 7c): the per-handle switch and the last batch's records
+// The optional per-batch outputs (engine.h BatchRecords; DESIGN.md §3 rules 7c, 7d, 7e): the
+// per-handle switch and the last batch's records.  One helper per operation; an entry point names
+// the handle's member, whose record type brings the texts (otm::kRecDesc).
 static_assert(sizeof(otm_matched_point) == 40 && alignof(otm_matched_point) == 8, "matched point record");
+static_assert(sizeof(otm_traversal) == 56 && alignof(otm_traversal) == 8, "traversal record");
+static_assert(sizeof(otm_point_score) == 32 && alignof(otm_point_score) == 4, "point score record");
 
-int otm_set_points(otm_engine* E, int on) {
+}  // extern "C"
+
+namespace {
+
+template <class Rec>
+using RecordsOf = otm::BatchRecords<Rec> otm_engine::*;
+
+template <class Rec>
+int records_set(otm_engine* E, RecordsOf<Rec> m, int on) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
   std::lock_guard<std::mutex> lk(E->mu);
-  for (otm_engine* m : E->members) {
-    std::lock_guard<std::mutex> ml(m->mu);
-    m->points_on = on != 0;
+  for (otm_engine* mem : E->members) {
+    std::lock_guard<std::mutex> ml(mem->mu);
+    (mem->*m).on = on != 0;
   }
-  E->points_on = on != 0;
+  (E->*m).on = on != 0;
   return OTM_OK;
 }
 
-int otm_points_info(const otm_engine* E, int* on) {
+template <class Rec>
+int records_info(const otm_engine* E, RecordsOf<Rec> m, int* on) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (on) *on = E->points_on ? 1 : 0;
+  if (on) *on = (E->*m).on ? 1 : 0;
   return OTM_OK;
 }
 
-static int otm_fetch_points_impl(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n_points) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "matched points: dst is NULL with cap != 0");
-  std::lock_guard<std::mutex> lk(E->mu);
-  if (!E->members.empty()) {
-    // the members' records of the group's last batch, joined in point order (group.cpp)
-    if (!E->points_on) return fail(OTM_EINVAL, "matched points are off (otm_set_points)");
-    if (E->g_pts_n < 0) return fail(OTM_EINVAL, "no batch has run with matched points on");
-    if (n_points) *n_points = E->g_pts_n;
-    if (!dst && cap == 0) return OTM_OK;
-    if (cap < E->g_pts_n) return fail(OTM_EINVAL, "matched points: cap below the batch's point count");
-    if (E->g_pts_n) std::memcpy(dst, E->g_pts.data(), (size_t)E->g_pts_n * sizeof(otm_matched_point));
-    return OTM_OK;
-  }
-  if (E->device >= 0) (void)hipSetDevice(E->device);
-  std::string err;
-  int rc = otm::engine_fetch_points(E, dst, cap, n_points, &err);
-  return rc ? fail(rc, err) : OTM_OK;
+// A multi-device handle answers out of its joined records (group.cpp; `offsets`: what the output
+// has beside them), a one-device handle through `one`, its engine-level fetch.
+template <class Rec, class One, class Offsets>
+int records_fetch(otm_engine* E, RecordsOf<Rec> m, Rec* dst, int64_t cap, int64_t* n, One one,
+                         Offsets offsets) {
+  return guarded([&] {
+    constexpr const otm::RecDesc& d = otm::kRecDesc<Rec>;
+    if (!E) return fail(OTM_EINVAL, "engine is NULL");
+    if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, d.dst_null);
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (!E->members.empty()) {
+      const otm::BatchRecords<Rec>& r = E->*m;
+      if (!r.on) return fail(OTM_EINVAL, d.off);
+      if (r.joined_n < 0) return fail(OTM_EINVAL, d.none);
+      if (n) *n = r.joined_n;
+      offsets();
+      if (!dst && cap == 0) return (int)OTM_OK;
+      if (cap < r.joined_n) return fail(OTM_EINVAL, d.cap);
+      if (r.joined_n) std::memcpy(dst, r.joined.data(), (size_t)r.joined_n * sizeof(Rec));
+      return (int)OTM_OK;
+    }
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    std::string err;
+    const int rc = one(&err);
+    return rc ? fail(rc, err) : (int)OTM_OK;
+  });
+}
+// ... of the per-point outputs
+template <class Rec>
+int records_fetch(otm_engine* E, RecordsOf<Rec> m, Rec* dst, int64_t cap, int64_t* n) {
+  return records_fetch(
+      E, m, dst, cap, n, [&](std::string* err) { return otm::engine_fetch_records(E, E->*m, dst, cap, n, err); }, [] {});
 }
 
-int otm_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n_points) {
-  try {
-    return otm_fetch_points_impl(E, dst, cap, n_points);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
-}
-
-int otm_points_device(otm_engine* E, const void** dev, int64_t* n_points) {
-  if (!E || !dev) return fail(OTM_EINVAL, "engine or dev is NULL");
+// The device array of a one-device engine; `prepare` (the route's dense form) runs first.
+template <class Rec, class Prepare>
+int records_device(otm_engine* E, RecordsOf<Rec> m, const void** dev, int64_t* n, Prepare prepare) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<Rec>;
+  if (!E || !dev) return fail(OTM_EINVAL, d.dev_null);
   if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
   std::lock_guard<std::mutex> lk(E->mu);
-  if (!E->points_on) return fail(OTM_EINVAL, "matched points are off (otm_set_points)");
-  if (E->pts_n < 0) return fail(OTM_EINVAL, "no batch has run with matched points on");
-  *dev = E->pts_n ? E->pts.p : nullptr;
-  if (n_points) *n_points = E->pts_n;
+  std::string err;
+  if (const int rc = prepare(&err)) return fail(rc, err);
+  const otm::BatchRecords<Rec>& r = E->*m;
+  if (!r.on) return fail(OTM_EINVAL, d.off);
+  if (r.n < 0) return fail(OTM_EINVAL, d.none);
+  *dev = r.n ? r.dev.p : nullptr;
+  if (n) *n = r.n;
   return OTM_OK;
 }
+int no_prepare(std::string*) { return OTM_OK; }
 
-// Matched route (DESIGN.md §3 rule 7d): the per-handle switch and the last batch's records
-static_assert(sizeof(otm_traversal) == 56 && alignof(otm_traversal) == 8, "traversal record");
+}  // namespace
 
-int otm_set_traversals(otm_engine* E, int on) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  std::lock_guard<std::mutex> lk(E->mu);
-  for (otm_engine* m : E->members) {
-    std::lock_guard<std::mutex> ml(m->mu);
-    m->trav_on = on != 0;
-  }
-  E->trav_on = on != 0;
-  return OTM_OK;
+extern "C" {
+
+int otm_set_points(otm_engine* E, int on) { return records_set(E, &otm_engine::points, on); }
+int otm_points_info(const otm_engine* E, int* on) { return records_info(E, &otm_engine::points, on); }
+int otm_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n_points) {
+  return records_fetch(E, &otm_engine::points, dst, cap, n_points);
+}
+int otm_points_device(otm_engine* E, const void** dev, int64_t* n_points) {
+  return records_device(E, &otm_engine::points, dev, n_points, no_prepare);
 }
 
-int otm_traversals_info(const otm_engine* E, int* on) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (on) *on = E->trav_on ? 1 : 0;
-  return OTM_OK;
+int otm_set_scores(otm_engine* E, int on) { return records_set(E, &otm_engine::scores, on); }
+int otm_scores_info(const otm_engine* E, int* on) { return records_info(E, &otm_engine::scores, on); }
+int otm_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n_points) {
+  return records_fetch(E, &otm_engine::scores, dst, cap, n_points);
 }
+int otm_scores_device(otm_engine* E, const void** dev, int64_t* n_points) {
+  return records_device(E, &otm_engine::scores, dev, n_points, no_prepare);
+}
+
+// The matched route has per-trace offsets beside its records, and a dense form that its first
+// size, fetch or device call of a batch makes (engine_traversals_dense).
+int otm_set_traversals(otm_engine* E, int on) { return records_set(E, &otm_engine::route, on); }
+int otm_traversals_info(const otm_engine* E, int* on) { return records_info(E, &otm_engine::route, on); }
 
 int otm_traversals_size(otm_engine* E, int64_t* n_traces, int64_t* n) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  try {
+  // (guarded_alloc: its std::mutex could in principle throw a std::system_error, which this call
+  // has never turned into a code)
+  return guarded_alloc([&] {
+    constexpr const otm::RecDesc& d = otm::kRecDesc<otm_traversal>;
     std::lock_guard<std::mutex> lk(E->mu);
     if (!E->members.empty()) {
-      if (!E->trav_on) return fail(OTM_EINVAL, "the matched route is off (otm_set_traversals)");
-      if (E->g_tv_n < 0) return fail(OTM_EINVAL, "no batch has run with the matched route on");
+      if (!E->route.on) return fail(OTM_EINVAL, d.off);
+      if (E->route.joined_n < 0) return fail(OTM_EINVAL, d.none);
       if (n_traces) *n_traces = (int64_t)E->g_tv_off.size() - 1;
-      if (n) *n = E->g_tv_n;
-      return OTM_OK;
+      if (n) *n = E->route.joined_n;
+      return (int)OTM_OK;
     }
     if (E->device >= 0) (void)hipSetDevice(E->device);
     std::string err;
     const int rc = otm::engine_traversals_dense(E, &err);
     if (rc) return fail(rc, err);
     if (n_traces) *n_traces = E->tv_T;
-    if (n) *n = E->tv_n;
-    return OTM_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  }
-}
-
-static int otm_fetch_traversals_impl(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "matched route: dst is NULL with cap != 0");
-  std::lock_guard<std::mutex> lk(E->mu);
-  if (!E->members.empty()) {
-    // the members' records of the group's last batch, joined in trace order (group.cpp)
-    if (!E->trav_on) return fail(OTM_EINVAL, "the matched route is off (otm_set_traversals)");
-    if (E->g_tv_n < 0) return fail(OTM_EINVAL, "no batch has run with the matched route on");
-    if (n) *n = E->g_tv_n;
-    if (trav_off) std::memcpy(trav_off, E->g_tv_off.data(), E->g_tv_off.size() * sizeof(int64_t));
-    if (!dst && cap == 0) return OTM_OK;
-    if (cap < E->g_tv_n) return fail(OTM_EINVAL, "matched route: cap below the batch's record count");
-    if (E->g_tv_n) std::memcpy(dst, E->g_tv.data(), (size_t)E->g_tv_n * sizeof(otm_traversal));
-    return OTM_OK;
-  }
-  if (E->device >= 0) (void)hipSetDevice(E->device);
-  std::string err;
-  int rc = otm::engine_fetch_traversals(E, dst, cap, trav_off, n, &err);
-  return rc ? fail(rc, err) : OTM_OK;
+    if (n) *n = E->route.n;
+    return (int)OTM_OK;
+  });
 }
 
 int otm_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n) {
-  try {
-    return otm_fetch_traversals_impl(E, dst, cap, trav_off, n);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return records_fetch(
+      E, &otm_engine::route, dst, cap, n,
+      [&](std::string* err) { return otm::engine_fetch_traversals(E, dst, cap, trav_off, n, err); },
+      [&] {
+        if (trav_off) std::memcpy(trav_off, E->g_tv_off.data(), E->g_tv_off.size() * sizeof(int64_t));
+      });
 }
 
 int otm_traversals_device(otm_engine* E, const void** recs, const int64_t** trav_off, int64_t* n) {
-  if (!E || !recs) return fail(OTM_EINVAL, "engine or recs is NULL");
-  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
-  std::lock_guard<std::mutex> lk(E->mu);
-  if (E->device >= 0) (void)hipSetDevice(E->device);
-  std::string err;
-  const int rc = otm::engine_traversals_dense(E, &err);
-  if (rc) return fail(rc, err);
-  *recs = E->tv_n ? E->tv_dense.p : nullptr;
-  if (trav_off) *trav_off = E->tv_off.p;
-  if (n) *n = E->tv_n;
-  return OTM_OK;
-}
-
-// Match scores (DESIGN.md §3 rule 7e): the per-handle switch and the last batch's records
-static_assert(sizeof(otm_point_score) == 32 && alignof(otm_point_score) == 4, "point score record");
-
-int otm_set_scores(otm_engine* E, int on) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  std::lock_guard<std::mutex> lk(E->mu);
-  for (otm_engine* m : E->members) {
-    std::lock_guard<std::mutex> ml(m->mu);
-    m->scores_on = on != 0;
-  }
-  E->scores_on = on != 0;
-  return OTM_OK;
-}
-
-int otm_scores_info(const otm_engine* E, int* on) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (on) *on = E->scores_on ? 1 : 0;
-  return OTM_OK;
-}
-
-static int otm_fetch_scores_impl(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n_points) {
-  if (!E) return fail(OTM_EINVAL, "engine is NULL");
-  if (cap < 0 || (!dst && cap != 0)) return fail(OTM_EINVAL, "match scores: dst is NULL with cap != 0");
-  std::lock_guard<std::mutex> lk(E->mu);
-  if (!E->members.empty()) {
-    // the members' records of the group's last batch, joined in point order (group.cpp)
-    if (!E->scores_on) return fail(OTM_EINVAL, "match scores are off (otm_set_scores)");
-    if (E->g_sc_n < 0) return fail(OTM_EINVAL, "no batch has run with match scores on");
-    if (n_points) *n_points = E->g_sc_n;
-    if (!dst && cap == 0) return OTM_OK;
-    if (cap < E->g_sc_n) return fail(OTM_EINVAL, "match scores: cap below the batch's point count");
-    if (E->g_sc_n) std::memcpy(dst, E->g_sc.data(), (size_t)E->g_sc_n * sizeof(otm_point_score));
-    return OTM_OK;
-  }
-  if (E->device >= 0) (void)hipSetDevice(E->device);
-  std::string err;
-  int rc = otm::engine_fetch_scores(E, dst, cap, n_points, &err);
-  return rc ? fail(rc, err) : OTM_OK;
-}
-
-int otm_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n_points) {
-  try {
-    return otm_fetch_scores_impl(E, dst, cap, n_points);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
-}
-
-int otm_scores_device(otm_engine* E, const void** dev, int64_t* n_points) {
-  if (!E || !dev) return fail(OTM_EINVAL, "engine or dev is NULL");
-  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
-  std::lock_guard<std::mutex> lk(E->mu);
-  if (!E->scores_on) return fail(OTM_EINVAL, "match scores are off (otm_set_scores)");
-  if (E->sc_n < 0) return fail(OTM_EINVAL, "no batch has run with match scores on");
-  *dev = E->sc_n ? E->sc.p : nullptr;
-  if (n_points) *n_points = E->sc_n;
-  return OTM_OK;
+  return records_device(E, &otm_engine::route, recs, n, [&](std::string* err) {
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    const int rc = otm::engine_traversals_dense(E, err);
+    if (!rc && trav_off) *trav_off = E->tv_off.p;
+    return rc;
+  });
 }
 
 int otm_index_tables(const otm_engine* E, int64_t* slots, int64_t* bytes, int32_t* load_pct) {
@@ -2526,127 +2500,53 @@ int otm_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t* ne
   return rc ? fail(rc, err) : OTM_OK;
 }
 
-// Entry points: nothing throws across the C ABI (an allocation failure or an
-// internal exception becomes an error code, or a 500 body).
+// Entry points: nothing throws across the C ABI (guarded, guarded_500 above).
 int otm_engine_create(const char* cfg_path, const int* devices, int ndev, otm_engine** out) {
-  try {
-    return otm_engine_create_impl(cfg_path, devices, ndev, out);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_engine_create_impl(cfg_path, devices, ndev, out); });
 }
 
 int otm_report_batch(otm_engine* E, int n, const char* const* reqs, const size_t* lens, char** resps,
                      size_t* resp_lens, int* codes) {
-  try {
-    return otm_report_batch_impl(E, n, reqs, lens, resps, resp_lens, codes);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_report_batch_impl(E, n, reqs, lens, resps, resp_lens, codes); });
 }
 
 int otm_report_segments_device(otm_engine* E, int n, const char* const* reqs, const size_t* lens,
                                const char* const* match_jsons, const size_t* match_lens, char** resps,
                                size_t* resp_lens, int* codes) {
-  try {
-    return otm_report_segments_device_impl(E, n, reqs, lens, match_jsons, match_lens, resps, resp_lens, codes);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded(
+      [&] { return otm_report_segments_device_impl(E, n, reqs, lens, match_jsons, match_lens, resps, resp_lens, codes); });
 }
 
 int otm_submit(otm_engine* E, const char* req, size_t len, uint64_t tag) {
-  try {
-    return otm_submit_impl(E, req, len, tag);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_submit_impl(E, req, len, tag); });
 }
 
 int otm_submit_batch(otm_engine* E, int n, const char* const* reqs, const size_t* lens, const uint64_t* tags) {
-  try {
-    return otm_submit_batch_impl(E, n, reqs, lens, tags);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_submit_batch_impl(E, n, reqs, lens, tags); });
 }
 
 int otm_match_soa(otm_engine* E, const otm_batch* in, otm_results* out) {
-  try {
-    return otm_match_soa_impl(E, in, out);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_match_soa_impl(E, in, out); });
 }
 
 int otm_match_compact(otm_engine* E, const otm_batch_compact* in, otm_results* out) {
-  try {
-    return otm_match_compact_impl(E, in, out);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_match_compact_impl(E, in, out); });
 }
 
 int otm_match_device(otm_engine* E, const otm_batch* in, void* stream) {
-  try {
-    return otm_match_device_impl(E, in, stream);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_match_device_impl(E, in, stream); });
 }
 
 int otm_fetch_results(otm_engine* E, otm_results* out) {
-  try {
-    return otm_fetch_results_impl(E, out);
-  } catch (const std::bad_alloc&) {
-    return fail(OTM_ENOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return fail(OTM_EINVAL, std::string("internal error: ") + e.what());
-  }
+  return guarded([&] { return otm_fetch_results_impl(E, out); });
 }
 
 int otm_report(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
-  try {
-    return otm_report_impl(E, req, len, resp, resp_len);
-  } catch (...) {
-    // a 500 like :239-240, its body allocated without anything that throws
-    static const char kBody[] = "{\"error\":\"internal error\"}";
-    char* b = (char*)std::malloc(sizeof kBody);
-    if (b) std::memcpy(b, kBody, sizeof kBody);
-    if (resp) *resp = b;
-    if (resp_len) *resp_len = b ? sizeof kBody - 1 : 0;
-    return 500;
-  }
+  return guarded_500(resp, resp_len, [&] { return otm_report_impl(E, req, len, resp, resp_len); });
 }
 
 int otm_match_json(otm_engine* E, const char* req, size_t len, char** resp, size_t* resp_len) {
-  try {
-    return otm_match_json_impl(E, req, len, resp, resp_len);
-  } catch (...) {
-    // a 500 like :239-240, its body allocated without anything that throws
-    static const char kBody[] = "{\"error\":\"internal error\"}";
-    char* b = (char*)std::malloc(sizeof kBody);
-    if (b) std::memcpy(b, kBody, sizeof kBody);
-    if (resp) *resp = b;
-    if (resp_len) *resp_len = b ? sizeof kBody - 1 : 0;
-    return 500;
-  }
+  return guarded_500(resp, resp_len, [&] { return otm_match_json_impl(E, req, len, resp, resp_len); });
 }
 
 }  // extern "C"

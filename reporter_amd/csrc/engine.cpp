@@ -386,9 +386,9 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->small_points = P->small_points;
   C->trans_lanes = P->trans_lanes;
   C->queue_kph = P->queue_kph;
-  C->points_on = P->points_on;
-  C->trav_on = P->trav_on;
-  C->scores_on = P->scores_on;
+  C->points.on = P->points.on;
+  C->route.on = P->route.on;
+  C->scores.on = P->scores.on;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -799,7 +799,7 @@ static int bind_trav(otm_engine* E, int32_t NT, int64_t NP, DevTrav& tv, std::st
 // The match scores' records, alpha scratch and packed-form list (rule 7e).
 static int bind_scores(otm_engine* E, int32_t NT, int64_t NP, DevScores& sc, std::string* err) {
   const size_t Pn = (size_t)NP + 1;
-  TRY(bind_buf(sc.rec, E->sc, Pn, err));
+  TRY(bind_buf(sc.rec, E->scores.dev, Pn, err));
   TRY(bind_buf(sc.alpha, E->sc_alpha, Pn * KIN, err));
   TRY(bind_buf(sc.alpha_x, E->sc_alpha_x, Pn * KX, err));
   TRY(bind_buf(sc.rej, E->sc_rej, (size_t)NT + 2, err));
@@ -818,11 +818,7 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
                              int from = RESUME_ALL) {
   const int64_t NP = b.n_points;
   const int32_t NT = b.n_traces;
-  // (any batch overwrites what the last one's matched route was made from: nothing of it stays fetchable,
-  // whatever becomes of this one)
-  E->tv_T = -1;
-  E->tv_n = -1;
-  E->sc_n = -1;  // (likewise the match scores)
+  end_records(E, REC_BATCH_BEGINS);
   DevWork w{};
   TRY(bind_point_work(E, NP, NT, w, err));
 
@@ -904,25 +900,25 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   if (E->queue_kph > 0.0f) launch_queue(b, w, o, E->queue_kph, s);
   // K7c (DESIGN.md §3 rule 7c): only with the handle's switch on; outside the timing marks.
   // Every attempt writes the whole array, so a redone or resumed batch leaves one run's records.
-  E->pts_n = -1;
-  if (E->points_on) {
-    TRY(E->pts.ensure((size_t)NP + 1, err));
-    launch_points(E->g, b, dp, w, E->pts.p, s);
-    E->pts_n = NP;
+  end_records(E, REC_BATCH_OUTPUTS);
+  if (records_wanted(E, E->points)) {
+    TRY(E->points.dev.ensure((size_t)NP + 1, err));
+    launch_points(E->g, b, dp, w, E->points.dev.p, s);
+    E->points.n = NP;
   }
   // K7e (DESIGN.md §3 rule 7e): beside K7c, only with the handle's switch on and only for a binary-level
   // batch; outside the timing marks.  It reads what K3-K5 left, which nothing after K5 writes before the
   // next batch, and trace_err as route recovery left it (launched after launch_route: K6 can still fail a
   // trace, whose records are then all zero); every attempt writes the whole array.
-  if (E->scores_on && E->tv_want) {
+  if (records_wanted(E, E->scores)) {
     DevScores sc{};
     TRY(bind_scores(E, NT, NP, sc, err));
     launch_scores(b, w, sc, s);
-    E->sc_n = NP;
+    E->scores.n = NP;
   }
   // K7d (DESIGN.md §3 rule 7d): likewise, and only for a binary-level batch.  Every attempt writes
   // each trace's whole count and region; the dense form is made at the first fetch.
-  if (E->trav_on && E->tv_want) {
+  if (records_wanted(E, E->route)) {
     DevTrav tv{};
     TRY(bind_trav(E, NT, NP, tv, err));
     HIPCHK(hipMemsetAsync(tv.cnt + NT, 0, sizeof *tv.cnt, s));
@@ -952,14 +948,13 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       if (cand) E->cand_final = 0;
     }
   } oom{E};
-  // a batch that fails leaves no match scores to fetch
-  struct ScoreGuard {
+  struct FailGuard {
     otm_engine* E;
     bool ok = false;
-    ~ScoreGuard() {
-      if (!ok) E->sc_n = -1;
+    ~FailGuard() {
+      if (!ok) end_records(E, REC_BATCH_FAILED);
     }
-  } scg{E};
+  } failed{E};
   int from = RESUME_ALL;
   DevWork grown{};  // (the tiers' tables as a growth below leaves them: the next attempt binds them again)
   E->last_resumes = 0;
@@ -1063,7 +1058,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
       for (int q = first[k]; q <= last[k]; ++q) E->stage_ms[k] += E->kernel_ms[q];
     }
   }
-  scg.ok = true;
+  failed.ok = true;
   return OTM_OK;
 }
 
@@ -1661,64 +1656,60 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
   return OTM_OK;
 }
 
-int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err) {
-  if (!E->points_on) {
-    *err = "matched points are off (otm_set_points)";
-    return OTM_EINVAL;
-  }
-  if (E->pts_n < 0) {
-    *err = "no batch has run with matched points on";
-    return OTM_EINVAL;
-  }
-  if (n) *n = E->pts_n;
-  if (!dst && cap == 0) return OTM_OK;  // sizing call
-  if (!dst || cap < E->pts_n) {
-    *err = "matched points: cap below the batch's point count";
-    return OTM_EINVAL;
-  }
-  const size_t bytes = (size_t)E->pts_n * sizeof(otm_matched_point);
-  if (!bytes) return OTM_OK;
-  TRY(E->h_pts.ensure((size_t)E->pts_n, err));
-  HIPCHK(big_copy(E->h_pts.p, E->pts.p, bytes, hipMemcpyDeviceToHost, E->stream));
-  HIPCHK(wait_batch(E, E->stream, E->pts_n));
-  std::memcpy(dst, E->h_pts.p, bytes);
-  return OTM_OK;
+template <class Rec>
+static void end_if(BatchRecords<Rec>& r, RecEvent event) {
+  if (kRecDesc<Rec>.ends & event) r.n = r.joined_n = -1;
 }
 
-int engine_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n, std::string* err) {
-  if (!E->scores_on) {
-    *err = "match scores are off (otm_set_scores)";
+void end_records(otm_engine* E, RecEvent event) {
+  end_if(E->points, event);
+  end_if(E->route, event);
+  end_if(E->scores, event);
+  if (kRecDesc<otm_traversal>.ends & event) E->tv_T = -1;  // (the regions its dense form is made from)
+}
+
+template <class Rec>
+int engine_fetch_records(otm_engine* E, BatchRecords<Rec>& r, Rec* dst, int64_t cap, int64_t* n, std::string* err) {
+  constexpr const RecDesc& d = kRecDesc<Rec>;
+  if (!r.on) {
+    *err = d.off;
     return OTM_EINVAL;
   }
-  if (E->sc_n < 0) {
-    *err = "no batch has run with match scores on";
+  if (r.n < 0) {
+    *err = d.none;
     return OTM_EINVAL;
   }
-  if (n) *n = E->sc_n;
+  if (n) *n = r.n;
   if (!dst && cap == 0) return OTM_OK;  // sizing call
-  if (!dst || cap < E->sc_n) {
-    *err = "match scores: cap below the batch's point count";
+  if (!dst || cap < r.n) {
+    *err = d.cap;
     return OTM_EINVAL;
   }
-  const size_t bytes = (size_t)E->sc_n * sizeof(otm_point_score);
+  const size_t bytes = (size_t)r.n * sizeof(Rec);
   if (!bytes) return OTM_OK;
-  TRY(E->h_sc.ensure((size_t)E->sc_n, err));
-  HIPCHK(big_copy(E->h_sc.p, E->sc.p, bytes, hipMemcpyDeviceToHost, E->stream));
-  HIPCHK(wait_batch(E, E->stream, E->sc_n));
-  std::memcpy(dst, E->h_sc.p, bytes);
+  TRY(r.pin.ensure((size_t)r.n, err));
+  HIPCHK(big_copy(r.pin.p, r.dev.p, bytes, hipMemcpyDeviceToHost, E->stream));
+  HIPCHK(wait_batch(E, E->stream, r.n));
+  std::memcpy(dst, r.pin.p, bytes);
   return OTM_OK;
 }
+template int engine_fetch_records(otm_engine*, BatchRecords<otm_matched_point>&, otm_matched_point*, int64_t, int64_t*,
+                                  std::string*);
+template int engine_fetch_records(otm_engine*, BatchRecords<otm_traversal>&, otm_traversal*, int64_t, int64_t*,
+                                  std::string*);
+template int engine_fetch_records(otm_engine*, BatchRecords<otm_point_score>&, otm_point_score*, int64_t, int64_t*,
+                                  std::string*);
 
 int engine_traversals_dense(otm_engine* E, std::string* err) {
-  if (!E->trav_on) {
-    *err = "the matched route is off (otm_set_traversals)";
+  if (!E->route.on) {
+    *err = kRecDesc<otm_traversal>.off;
     return OTM_EINVAL;
   }
   if (E->tv_T < 0) {
-    *err = "no batch has run with the matched route on";
+    *err = kRecDesc<otm_traversal>.none;
     return OTM_EINVAL;
   }
-  if (E->tv_n >= 0) return OTM_OK;  // made by an earlier call for this batch
+  if (E->route.n >= 0) return OTM_OK;  // made by an earlier call for this batch
   hipStream_t s = E->stream;
   const int32_t NT = E->tv_T;
   // dense offsets: the exclusive scan of the per-trace counts, then one copy
@@ -1730,32 +1721,20 @@ int engine_traversals_dense(otm_engine* E, std::string* err) {
   HIPCHK(hipMemcpyAsync(E->h_tv_off.p, E->tv_off.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(wait_batch(E, s, E->last_P));
   const int64_t n = E->h_tv_off.p[NT];
-  TRY(E->tv_dense.ensure((size_t)n + 1, err));
+  TRY(E->route.dev.ensure((size_t)n + 1, err));
   if (NT && n) {
-    launch_trav_compact(NT, E->seg_ub.p, E->tv_off.p, E->tv_rec.p, E->tv_dense.p, s);
+    launch_trav_compact(NT, E->seg_ub.p, E->tv_off.p, E->tv_rec.p, E->route.dev.p, s);
     HIPCHK(hipGetLastError());
   }
-  E->tv_n = n;
+  E->route.n = n;
   return OTM_OK;
 }
 
 int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
                             std::string* err) {
   TRY(engine_traversals_dense(E, err));
-  if (n) *n = E->tv_n;
   if (trav_off) std::memcpy(trav_off, E->h_tv_off.p, ((size_t)E->tv_T + 1) * 8);
-  if (!dst && cap == 0) return OTM_OK;  // sizing call
-  if (!dst || cap < E->tv_n) {
-    *err = "matched route: cap below the batch's record count";
-    return OTM_EINVAL;
-  }
-  const size_t bytes = (size_t)E->tv_n * sizeof(otm_traversal);
-  if (!bytes) return OTM_OK;
-  TRY(E->h_tv.ensure((size_t)E->tv_n, err));
-  HIPCHK(big_copy(E->h_tv.p, E->tv_dense.p, bytes, hipMemcpyDeviceToHost, E->stream));
-  HIPCHK(wait_batch(E, E->stream, E->tv_n));
-  std::memcpy(dst, E->h_tv.p, bytes);
-  return OTM_OK;
+  return engine_fetch_records(E, E->route, dst, cap, n, err);
 }
 
 int engine_spill_stats(otm_engine* E, otm_spill_stats* out) {

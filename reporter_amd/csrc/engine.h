@@ -42,6 +42,62 @@ struct H2DOrder {
   hipStream_t copy = nullptr;
   bool own_queue = false;
 };
+// ---- Optional per-batch outputs: matched points (rule 7c), the matched route
+// (7d), match scores (7e).  Each is a switch on the handle and one array of
+// records that the last batch left, fetched any number of times until an
+// event ends them.
+//
+// What can end an output's records.  A fetch after it answers OTM_EINVAL
+// (RecDesc::none), never another batch's records.
+enum RecEvent : unsigned {
+  REC_BATCH_BEGINS = 1,   // a batch starts in this handle's buffers (every attempt of it)
+  REC_BATCH_OUTPUTS = 2,  // ... reaches its optional outputs (a multi-device engine: joins its members')
+  REC_BATCH_FAILED = 4,   // ... failed
+  REC_OTHER_CALL = 8,     // a JSON-level call on this handle, wherever its batches run
+};
+// An output's constants: the texts it answers through otm_last_error, and its
+// validity rule.
+struct RecDesc {
+  const char *off, *none, *cap, *dst_null, *dev_null;
+  bool binary_only;  // only a binary-level batch (otm_engine::binary_batch) writes records
+  unsigned ends;     // the RecEvents that end them (end_records)
+};
+template <class Rec>
+inline constexpr RecDesc kRecDesc{};
+// The validity table.  The three rules differ, as otmatch.h documents them:
+//  - matched points came first and any kind of batch writes them: records stand until the next batch
+//    with its outputs in this handle's buffers replaces them (REC_BATCH_OUTPUTS), so a batch that fails
+//    before that point, and a JSON call, leave the last ones fetchable;
+//  - the matched route is read out of the batch's segment regions, which any batch in these buffers
+//    overwrites from its start (REC_BATCH_BEGINS).  A JSON call that runs on batch contexts of its own
+//    (a split otm_report_batch) leaves the handle's buffers, and so the route, standing;
+//  - match scores promise "the handle's last call": every event but the outputs stage ends them, a JSON
+//    call even when it ran elsewhere.
+template <>
+inline constexpr RecDesc kRecDesc<otm_matched_point>{
+    "matched points are off (otm_set_points)", "no batch has run with matched points on",
+    "matched points: cap below the batch's point count", "matched points: dst is NULL with cap != 0",
+    "engine or dev is NULL", false, REC_BATCH_OUTPUTS};
+template <>
+inline constexpr RecDesc kRecDesc<otm_traversal>{
+    "the matched route is off (otm_set_traversals)", "no batch has run with the matched route on",
+    "matched route: cap below the batch's record count", "matched route: dst is NULL with cap != 0",
+    "engine or recs is NULL", true, REC_BATCH_BEGINS};
+template <>
+inline constexpr RecDesc kRecDesc<otm_point_score>{
+    "match scores are off (otm_set_scores)", "no batch has run with match scores on",
+    "match scores: cap below the batch's point count", "match scores: dst is NULL with cap != 0",
+    "engine or dev is NULL", true, REC_BATCH_BEGINS | REC_BATCH_FAILED | REC_OTHER_CALL};
+
+template <class Rec>
+struct BatchRecords {
+  bool on = false;             // the handle's switch (otm_set_*)
+  int64_t n = -1;              // records of the last batch that left any (-1: none to fetch)
+  DevBuf<Rec> dev;             // ... on the device
+  PinBuf<Rec> pin;             // the fetch's pinned staging
+  std::vector<Rec> joined;     // a multi-device engine: its members' records in batch order
+  int64_t joined_n = -1;       // ... their count, as n
+};
 }  // namespace otm
 
 struct otm_engine {
@@ -281,45 +337,25 @@ struct otm_engine {
   std::mutex split_mu;
   otm::H2DOrder split_order;
   std::atomic<int> last_split{1};  // the chunks of the last otm_report_batch (otm_debug_last_split)
-  // matched points (otm_set_points, DESIGN.md §3 rule 7c): off, a batch launches and allocates
-  // nothing for them.  pts: otm_matched_point[last_P] of the
-  // last batch that ran with the switch on (pts_n its count, -1: none); h_pts: the pinned staging of
-  // otm_fetch_points; g_pts: a multi-device engine's joined records (g_pts_n as pts_n)
-  bool points_on = false;
-  int64_t pts_n = -1, g_pts_n = -1;
-  otm::DevBuf<otm_matched_point> pts;
-  otm::PinBuf<otm_matched_point> h_pts;
-  std::vector<otm_matched_point> g_pts;
-  // matched route (otm_set_traversals, DESIGN.md §3 rule 7d): off, a batch launches and allocates
-  // nothing for it; on, only a binary-level batch does (a JSON, request or batcher batch on the handle
-  // writes none and leaves none to fetch).  tv_rec / tv_cnt: DevTrav's regions and counts of the last
-  // such batch (tv_T its trace count, -1: none); tv_off / tv_dense: the counts' scan and the dense
-  // records, made at the first fetch or device call (tv_n their number, -1: not made yet); h_tv /
-  // h_tv_off: the pinned staging of otm_fetch_traversals; g_tv / g_tv_off: a multi-device engine's
-  // joined records and offsets (g_tv_n their number, -1: none)
-  bool trav_on = false;
-  bool tv_want = false;  // the batch in flight is a binary-level one (abi.cpp BinaryBatch): only those keep records
+  // the optional per-batch outputs (otm::BatchRecords above; DESIGN.md §3 rules 7c, 7d, 7e): off, a
+  // batch launches and allocates nothing for them
+  bool binary_batch = false;  // the batch in flight is a binary-level one (abi.cpp BinaryBatch)
+  otm::BatchRecords<otm_matched_point> points;  // otm_matched_point[last_P] (k_points)
+  // the matched route: route.dev is the dense form, made at the first fetch or device call of a batch
+  // (route.n: -1 until then).  tv_rec / tv_cnt: DevTrav's regions and counts as the batch wrote them
+  // (tv_T its trace count, -1: no batch left any); tv_off / h_tv_off: the counts' scan and its pinned
+  // copy; g_tv_off: a multi-device engine's joined offsets
+  otm::BatchRecords<otm_traversal> route;
   int32_t tv_T = -1;
-  int64_t tv_n = -1, g_tv_n = -1;
-  otm::DevBuf<otm_traversal> tv_rec, tv_dense;
+  otm::DevBuf<otm_traversal> tv_rec;
   otm::DevBuf<int64_t> tv_cnt, tv_off;
-  otm::PinBuf<otm_traversal> h_tv;
   otm::PinBuf<int64_t> h_tv_off;
-  std::vector<otm_traversal> g_tv;
   std::vector<int64_t> g_tv_off;
-  // match scores (otm_set_scores, DESIGN.md §3 rule 7e): off, a batch launches and allocates nothing
-  // for them; on, only a binary-level batch does (tv_want), and any other batch, or a failed one, leaves
-  // none to fetch.  sc: otm_point_score[last_P] of the last such batch (sc_n its count, -1: none);
-  // sc_alpha / sc_alpha_x: K7e's alpha scratch in the candidates' layout; sc_rej: the packed form's
-  // list (its count in the last element); h_sc: the pinned staging of otm_fetch_scores; g_sc: a
-  // multi-device engine's joined records (g_sc_n as sc_n)
-  bool scores_on = false;
-  int64_t sc_n = -1, g_sc_n = -1;
-  otm::DevBuf<otm_point_score> sc;
+  // the match scores: otm_point_score[last_P] (k_scores).  sc_alpha / sc_alpha_x: K7e's alpha scratch
+  // in the candidates' layout; sc_rej: the packed form's list (its count in the last element)
+  otm::BatchRecords<otm_point_score> scores;
   otm::DevBuf<float> sc_alpha, sc_alpha_x;
   otm::DevBuf<int32_t> sc_rej;
-  otm::PinBuf<otm_point_score> h_sc;
-  std::vector<otm_point_score> g_sc;
 };
 
 namespace otm {
@@ -379,18 +415,23 @@ int engine_copy_responses(otm_engine* E, char* dst, int64_t total, const char** 
 // copy results of the last batch to host vectors and describe them
 int engine_fetch(otm_engine* E, otm_results* out, std::string* err);
 int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t* needed, std::string* err);
-// the last batch's matched points (E->pts_n of them) copied to dst; OTM_EINVAL
-// when the switch is off, no batch ran with it on, or cap is below the count
-int engine_fetch_points(otm_engine* E, otm_matched_point* dst, int64_t cap, int64_t* n, std::string* err);
-// the last batch's match scores (E->sc_n of them) copied to dst; OTM_EINVAL as
-// engine_fetch_points
-int engine_fetch_scores(otm_engine* E, otm_point_score* dst, int64_t cap, int64_t* n, std::string* err);
-// the last batch's matched route: compacts the regions on the device (once per
-// batch; E->tv_dense, E->tv_off, E->tv_n); OTM_EINVAL when the switch is off or
-// no batch ran with it on
+// whether the batch in flight on E writes this output
+template <class Rec>
+inline bool records_wanted(const otm_engine* E, const BatchRecords<Rec>& r) {
+  return r.on && (!kRecDesc<Rec>.binary_only || E->binary_batch);
+}
+// ends the records of every output that `event` ends (the kRecDesc table); the caller holds E->mu
+void end_records(otm_engine* E, RecEvent event);
+// r's records (r.n of them, r.dev) copied to dst[cap], *n their count; cap 0 with dst null only
+// sizes.  OTM_EINVAL when the switch is off, there are none to fetch, or cap is below the count.
+// (Instantiated in engine.cpp for the three outputs.)
+template <class Rec>
+int engine_fetch_records(otm_engine* E, BatchRecords<Rec>& r, Rec* dst, int64_t cap, int64_t* n, std::string* err);
+// the matched route's preparation: compacts the last batch's regions on the device (once per
+// batch; E->route.dev, E->tv_off, E->route.n); OTM_EINVAL when the switch is off or no batch ran
+// with it on
 int engine_traversals_dense(otm_engine* E, std::string* err);
-// ... and copies the dense records to dst[cap] and the tv_T + 1 offsets to
-// trav_off (may be null); OTM_EINVAL also when cap is below the count
+// ... then engine_fetch_records, and the tv_T + 1 offsets to trav_off (may be null)
 int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
                             std::string* err);
 int engine_counters(otm_engine* E, otm_work_counters* out);

@@ -130,10 +130,12 @@ void run_member(otm_engine* M, MemberOut& o) {
   sb.accuracy = o.acc.data();
   std::lock_guard<std::mutex> lk(M->mu);
   (void)hipSetDevice(M->device);
-  if (M->group) M->points_on = M->group->points_on;  // a group's batch runs with the group handle's switch
-  if (M->group) M->trav_on = M->group->trav_on;
-  if (M->group) M->scores_on = M->group->scores_on;
-  if (M->group) M->tv_want = M->group->tv_want;
+  if (M->group) {  // a group's batch runs with the group handle's switches
+    M->points.on = M->group->points.on;
+    M->route.on = M->group->route.on;
+    M->scores.on = M->group->scores.on;
+    M->binary_batch = M->group->binary_batch;
+  }
   otm_results r;
   o.rc = engine_match_host(M, &sb, &o.err);
   if (!o.rc) o.rc = engine_fetch(M, &r, &o.err);
@@ -143,17 +145,15 @@ void run_member(otm_engine* M, MemberOut& o) {
   o.segs.assign(r.segments, r.segments + r.n_segments);
   o.reps.assign(r.reports, r.reports + r.n_reports);
   o.ways.assign(r.way_ids, r.way_ids + r.n_way_ids);
-  if (M->points_on) {
+  const auto fetch_per_point = [&](auto& r, auto& recs) {
+    if (!records_wanted(M, r) || o.rc) return;
     int64_t n = 0;
-    o.pts.resize((size_t)sb.n_points);
-    o.rc = engine_fetch_points(M, o.pts.data(), sb.n_points, &n, &o.err);
-  }
-  if (M->scores_on && M->tv_want && !o.rc) {
-    int64_t n = 0;
-    o.sc.resize((size_t)sb.n_points);
-    o.rc = engine_fetch_scores(M, o.sc.data(), sb.n_points, &n, &o.err);
-  }
-  if (M->trav_on && M->tv_want && !o.rc) {
+    recs.resize((size_t)sb.n_points);
+    o.rc = engine_fetch_records(M, r, recs.data(), sb.n_points, &n, &o.err);
+  };
+  fetch_per_point(M->points, o.pts);
+  fetch_per_point(M->scores, o.sc);
+  if (records_wanted(M, M->route) && !o.rc) {
     int64_t n = 0;
     o.tv_off.resize((size_t)sb.n_traces + 1);
     o.rc = engine_fetch_traversals(M, nullptr, 0, o.tv_off.data(), &n, &o.err);
@@ -165,8 +165,7 @@ void run_member(otm_engine* M, MemberOut& o) {
 int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_results* out, std::string* err) {
   const int nd = (int)G->members.size();
   const int32_t nt = b->n_traces;
-  G->g_tv_n = -1;  // (any batch of the group ends the last one's matched route)
-  G->g_sc_n = -1;  // (... and match scores)
+  end_records(G, REC_BATCH_BEGINS);
   const int64_t p0 = nt > 0 ? b->trace_off[0] : 0;
   const int64_t np = nt > 0 ? b->trace_off[nt] - p0 : 0;
   std::vector<MemberOut> mo((size_t)nd);
@@ -226,6 +225,7 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
   G->member_pool->run(tasks);
   for (const MemberOut& o : mo)
     if (o.rc) {
+      end_records(G, REC_BATCH_FAILED);
       *err = o.err;
       return o.rc;
     }
@@ -250,38 +250,32 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
     G->g_reps.insert(G->g_reps.end(), o.reps.begin() + r0, o.reps.begin() + r0 + tr.rep_cnt);
     G->g_traces[(size_t)t] = tr;
   }
-  // the members' matched points, joined in the batch's point order
-  G->g_pts_n = -1;
-  if (G->points_on) {
-    G->g_pts.resize((size_t)np);
+  // the members' per-point records (matched points, match scores), joined in the batch's point order
+  end_records(G, REC_BATCH_OUTPUTS);
+  const auto join_per_point = [&](auto& r, auto MemberOut::*recs) {
+    if (!records_wanted(G, r)) return;
+    r.joined.resize((size_t)np);
     for (int32_t t = 0; t < nt; ++t) {
       const MemberOut& o = mo[(size_t)mem[(size_t)t]];
       const int64_t m0 = o.off[(size_t)pos[(size_t)t]], m1 = o.off[(size_t)pos[(size_t)t] + 1];
-      std::copy(o.pts.begin() + m0, o.pts.begin() + m1, G->g_pts.begin() + (b->trace_off[t] - p0));
+      std::copy((o.*recs).begin() + m0, (o.*recs).begin() + m1, r.joined.begin() + (b->trace_off[t] - p0));
     }
-    G->g_pts_n = np;
-  }
-  // the members' match scores, joined in the batch's point order
-  if (G->scores_on && G->tv_want) {
-    G->g_sc.resize((size_t)np);
-    for (int32_t t = 0; t < nt; ++t) {
-      const MemberOut& o = mo[(size_t)mem[(size_t)t]];
-      const int64_t m0 = o.off[(size_t)pos[(size_t)t]], m1 = o.off[(size_t)pos[(size_t)t] + 1];
-      std::copy(o.sc.begin() + m0, o.sc.begin() + m1, G->g_sc.begin() + (b->trace_off[t] - p0));
-    }
-    G->g_sc_n = np;
-  }
+    r.joined_n = np;
+  };
+  join_per_point(G->points, &MemberOut::pts);
+  join_per_point(G->scores, &MemberOut::sc);
   // the members' matched routes, joined in the batch's trace order (every field is trace-relative)
-  if (G->trav_on && G->tv_want) {
-    G->g_tv.clear();
+  if (records_wanted(G, G->route)) {
+    std::vector<otm_traversal>& g_tv = G->route.joined;
+    g_tv.clear();
     G->g_tv_off.assign((size_t)nt + 1, 0);
     for (int32_t t = 0; t < nt; ++t) {
       const MemberOut& o = mo[(size_t)mem[(size_t)t]];
       const int64_t m0 = o.tv_off[(size_t)pos[(size_t)t]], m1 = o.tv_off[(size_t)pos[(size_t)t] + 1];
-      G->g_tv.insert(G->g_tv.end(), o.tv.begin() + m0, o.tv.begin() + m1);
-      G->g_tv_off[(size_t)t + 1] = (int64_t)G->g_tv.size();
+      g_tv.insert(g_tv.end(), o.tv.begin() + m0, o.tv.begin() + m1);
+      G->g_tv_off[(size_t)t + 1] = (int64_t)g_tv.size();
     }
-    G->g_tv_n = (int64_t)G->g_tv.size();
+    G->route.joined_n = (int64_t)g_tv.size();
   }
   out->n_traces = nt;
   out->n_segments = (int32_t)G->g_segs.size();

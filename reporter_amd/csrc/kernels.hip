@@ -3898,6 +3898,27 @@ __device__ __forceinline__ int wave_incl_max(int v, int lane) {
   }
   return v;
 }
+// Segmented inclusive max-scan over the wave: a lane with `head` begins a
+// segment, and a lane whose segment began before the wave (no head up to it)
+// continues from `carry`, the segment's maximum so far -- the caller carries
+// lane 63's result to its next 64-point chunk (k_points' OTM_PT_ANCHOR,
+// k_traversals' largest offset of the open traversal).  A segment that
+// crosses a chunk is in the tests' cases stop_80 (80 interpolated points of
+// one step around point 64, every one an anchor) and hand_long_edge (a
+// traversal open from point 1 to past point 64, closed at its largest offset).
+__device__ __forceinline__ float wave_seg_incl_max(float v, bool head, float carry, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float vn = __shfl_up(v, d, 64);
+    const int hn = __shfl_up((int)head, d, 64);
+    if (lane >= d) {
+      if (!head) v = vn > v ? vn : v;
+      head = head || hn != 0;
+    }
+  }
+  if (!head) v = carry > v ? carry : v;
+  return v;
+}
 
 // what a state contributes (recomputed in the two passes that need it).
 // Every global load of a state is issued at once, unconditionally -- none
@@ -4667,8 +4688,20 @@ struct RoutePiece {
   int32_t edge;
   float o0, o1, xs;
 };
-__device__ float interp_pos(const DevGraph& g, const DevBatch& b, const DevParams& P, const DevWork& w, int64_t q,
-                            int64_t p, int64_t k) {
+// Where rule 7 puts point k: its position along the step's route (-1: none),
+// the winning piece's edge and the admissible foot's offset on it (edge -1:
+// none) -- the place the position names, xs + (off - o0).  One loop, tie rule
+// and set of f32 expressions for both users; each keeps only what it takes:
+// K7a the position (FOOT false; edge and off stay unset), rule 7c the edge and
+// offset (FOOT true; pos stays unset), so K7a's path gets no store.
+struct RoutePlace {
+  float pos;
+  int32_t edge;
+  float off;
+};
+template <bool FOOT>
+__device__ __forceinline__ RoutePlace place_on_route(const DevGraph& g, const DevBatch& b, const DevParams& P,
+                                                     const DevWork& w, int64_t q, int64_t p, int64_t k) {
   const int2 ci = w.chosen[q], cj = w.chosen[p];
   const int32_t ei = ci.x, ej = cj.x;
   const float oi = __int_as_float(ci.y), oj = __int_as_float(cj.y);
@@ -4680,7 +4713,8 @@ __device__ float interp_pos(const DevGraph& g, const DevBatch& b, const DevParam
   const float lat = b.lat[k], lon = b.lon[k];
   const float ls = MPD_F * cos_deg(lat);
   const float gcd = gc_dist(b.lat[q], b.lon[q], lat, lon);
-  float best = INFINITY, bpos = -1.0f, dd = 0.0f;
+  float best = INFINITY, bpos = -1.0f, dd = 0.0f, bo = 0.0f;
+  int32_t be = -1;
   for (int m = 0; m < npc; ++m) {
     RoutePiece pc;
     const int pk = m - (has0 ? 1 : 0);
@@ -4702,12 +4736,25 @@ __device__ float interp_pos(const DevGraph& g, const DevBatch& b, const DevParam
     if (!(boff >= pc.o0 && boff <= pc.o1)) continue;
     const float pos = pc.xs + (boff - pc.o0);
     const float cost = bsq / ds + fabsf(pos - gcd) / P.beta;
-    if (cost < best) {
+    if (cost < best) {  // (strict: of equal pieces the earliest wins)
       best = cost;
-      bpos = pos;
+      if constexpr (FOOT) {
+        be = pc.edge;
+        bo = boff;
+      } else {
+        bpos = pos;
+      }
     }
   }
-  return bpos;
+  return RoutePlace{bpos, be, bo};
+}
+
+// The step q -> p around interpolated point k, if there is one: linked, not a
+// chain start, matched, with a route.  The caller tests trace_err.
+__device__ __forceinline__ bool interp_step(const DevWork& w, int64_t k, int32_t& q, int32_t& p) {
+  q = w.prevc[k];
+  p = q >= 0 ? w.nextc[q] : -1;
+  return p >= 0 && w.col_prev[p] == q && !w.chain_start[p] && w.state[p] >= 0 && w.path_len[p] >= 0;
 }
 
 // Traversals a matched point can add: the close of the open traversal, its
@@ -4737,14 +4784,12 @@ __global__ __launch_bounds__(256) void k_seg_bound(DevGraph g, DevBatch b, DevPa
         v = 2 + (pl > 0 ? pl : 0);
       }
     } else {
-      // the step q -> p around this point: linked, matched, leaving q's edge
-      const int32_t q = w.prevc[k];
-      const int32_t p = q >= 0 ? w.nextc[q] : -1;
-      if (p >= 0 && w.col_prev[p] == q && !w.chain_start[p] && w.state[p] >= 0 && w.path_len[p] >= 0 &&
-          w.trace_err[t] == 0) {
+      // the step q -> p around this point, where it leaves q's edge
+      int32_t q, p;
+      if (interp_step(w, k, q, p) && w.trace_err[t] == 0) {
         const int2 ci = w.chosen[q], cj = w.chosen[p];
         if (!same_edge_step(ci.x, __int_as_float(ci.y), cj.x, __int_as_float(cj.y)))
-          w.ipos[k] = interp_pos(g, b, P, w, q, p, k);
+          w.ipos[k] = place_on_route<false>(g, b, P, w, q, p, k).pos;
       }
     }
   }
@@ -4851,54 +4896,6 @@ __global__ __launch_bounds__(1024) void k_fetch_scan(int32_t n, const int32_t* c
 
 // ============================================================== K7c matched points
 // (after the pipeline's other kernels in this file, so that the code object lays those out as it did without it)
-// interp_pos's sibling (DESIGN.md §3 rule 7c): the same loop, tie rules and
-// f32 expressions, returning the winning piece's edge and the admissible
-// foot's offset on it instead of the route position (edge -1: none), so K7a's
-// path gets no store and the place is the one ipos names: xs + (off - o0).
-__device__ int2 interp_foot(const DevGraph& g, const DevBatch& b, const DevParams& P, const DevWork& w, int64_t q,
-                            int64_t p, int64_t k) {
-  const int2 ci = w.chosen[q], cj = w.chosen[p];
-  const int32_t ei = ci.x, ej = cj.x;
-  const float oi = __int_as_float(ci.y), oj = __int_as_float(cj.y);
-  const int32_t poff = w.path_off[p], plen = w.path_len[p];
-  const bool has0 = !cand_node(oi);
-  const int npc = (has0 ? 1 : 0) + plen + (cand_node(oj) ? 0 : 1);
-  const float start = src_start(g, ei, oi);
-  const float ds = (2.0f * P.sigma_z) * P.sigma_z;
-  const float lat = b.lat[k], lon = b.lon[k];
-  const float ls = MPD_F * cos_deg(lat);
-  const float gcd = gc_dist(b.lat[q], b.lon[q], lat, lon);
-  float best = INFINITY, dd = 0.0f, bo = 0.0f;
-  int32_t be = -1;
-  for (int m = 0; m < npc; ++m) {
-    RoutePiece pc;
-    const int pk = m - (has0 ? 1 : 0);
-    const bool mid = !(has0 && m == 0) && pk < plen;
-    const int32_t e = has0 && m == 0 ? ei : (mid ? w.path_pool[poff + pk] : ej);
-    const int4 er = g.e_proj[e];
-    const float len = __int_as_float(er.z);
-    if (has0 && m == 0) {
-      pc = RoutePiece{e, oi, len, 0.0f};
-    } else if (mid) {
-      pc = RoutePiece{e, 0.0f, len, start + dd};
-      dd = dd + len;
-    } else {
-      pc = RoutePiece{e, 0.0f, oj, start + dd};
-    }
-    float bsq, boff;
-    project_edge(g, er, lat, lon, ls, bsq, boff);
-    if (!(boff >= pc.o0 && boff <= pc.o1)) continue;
-    const float pos = pc.xs + (boff - pc.o0);
-    const float cost = bsq / ds + fabsf(pos - gcd) / P.beta;
-    if (cost < best) {
-      best = cost;
-      be = pc.edge;
-      bo = boff;
-    }
-  }
-  return make_int2(be, __float_as_int(bo));
-}
-
 // The closest foot of point k on the whole of edge e (rule 7c, same-edge
 // steps): every shape segment, ties to the lowest, clamped into [lo, hi].
 __device__ float edge_foot(const DevGraph& g, const DevBatch& b, int32_t e, int64_t k, float lo, float hi) {
@@ -4950,10 +4947,8 @@ __global__ __launch_bounds__(TB) void k_points(DevGraph g, DevBatch b, DevParams
             flags |= OTM_PT_MATCHED | (cand_node(off) ? OTM_PT_NODE : 0u) | (w.chain_start[k] ? OTM_PT_CHAIN_START : 0u);
           }
         } else if (ok) {
-          // the step q -> p around this point: linked, matched (k_seg_bound's test)
-          const int32_t q = w.prevc[k];
-          const int32_t p = q >= 0 ? w.nextc[q] : -1;
-          if (p >= 0 && w.col_prev[p] == q && !w.chain_start[p] && w.state[p] >= 0 && w.path_len[p] >= 0) {
+          int32_t q, p;
+          if (interp_step(w, k, q, p)) {
             const int2 ci = w.chosen[q], cj = w.chosen[p];
             const float oi = __int_as_float(ci.y), oj = __int_as_float(cj.y);
             if (same_edge_step(ci.x, oi, cj.x, oj)) {
@@ -4963,9 +4958,9 @@ __global__ __launch_bounds__(TB) void k_points(DevGraph g, DevBatch b, DevParams
             } else {
               x = w.ipos[k];
               if (x >= 0.0f) {
-                const int2 f = interp_foot(g, b, P, w, q, p, k);
-                edge = f.x;
-                off = __int_as_float(f.y);
+                const RoutePlace f = place_on_route<true>(g, b, P, w, q, p, k);
+                edge = f.edge;
+                off = f.off;
                 flags = OTM_PT_MATCHED | OTM_PT_ROUTE;
               } else {
                 x = -1.0f;
@@ -4974,19 +4969,8 @@ __global__ __launch_bounds__(TB) void k_points(DevGraph g, DevBatch b, DevParams
           }
         }
       }
-      // segmented inclusive max-scan of x: a column (or a lane past the trace) starts a segment
-      float v = x;
-      bool head = col || !in;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float vn = __shfl_up(v, d, 64);
-        const int hn = __shfl_up((int)head, d, 64);
-        if (lane >= d) {
-          if (!head) v = vn > v ? vn : v;
-          head = head || hn != 0;
-        }
-      }
-      if (!head) v = carry > v ? carry : v;
+      // the step's running maximum of x: a column (or a lane past the trace) starts a segment
+      const float v = wave_seg_incl_max(x, col || !in, carry, lane);
       carry = __shfl(v, 63, 64);
       if ((flags & OTM_PT_ROUTE) && x >= v) flags |= OTM_PT_ANCHOR;
       if (!in) continue;
@@ -5186,18 +5170,7 @@ __global__ __launch_bounds__(TB) void k_traversals(DevGraph g, DevBatch b, DevWo
         x_off0 = c_off0;
         x_sh0 = c_sh0;
       }
-      float v = isst ? oj : -1.0f;
-      bool head = opener;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float vn = __shfl_up(v, d, 64);
-        const int hn = __shfl_up((int)head, d, 64);
-        if (lane >= d) {
-          if (!head) v = vn > v ? vn : v;
-          head = head || hn != 0;
-        }
-      }
-      if (!head) v = c_max > v ? c_max : v;
+      const float v = wave_seg_incl_max(isst ? oj : -1.0f, opener, c_max, lane);
       float cmx = __shfl_up(v, 1, 64);  // the open traversal's largest offset before this lane
       if (lane == 0) cmx = c_max;
       // ---- the final close of the chain that ends before this lane

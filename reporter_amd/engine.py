@@ -443,43 +443,56 @@ class Engine(object):
         _check(lib().otm_queue_info(self.h, C.byref(k)))
         return k.value
 
+    # The optional per-batch outputs (matched points, matched route, match
+    # scores): one switch, one info call, one fetch and one device call each,
+    # the same but for the C function's name and the record's dtype.
+    def _set_switch(self, fn, on):
+        _check(getattr(lib(), fn)(self.h, 1 if on else 0))
+
+    def _switch_info(self, fn):
+        on = C.c_int()
+        _check(getattr(lib(), fn)(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def _fetch_per_point(self, fn, dtype):
+        fetch, n = getattr(lib(), fn), C.c_int64()
+        _check(fetch(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        _check(fetch(self.h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
+
+    def _records_device(self, fn, pointers=1):
+        ptrs, n = [C.c_void_p() for _ in range(pointers)], C.c_int64()
+        _check(getattr(lib(), fn)(self.h, *[C.byref(p) for p in ptrs], C.byref(n)))
+        return tuple(p.value or 0 for p in ptrs) + (n.value,)
+
     def set_points(self, on):
         """The matched-points switch of this handle (otm_set_points; a multi-device
         engine passes it to every member, a clone inherits it when it is made)."""
-        _check(lib().otm_set_points(self.h, 1 if on else 0))
+        self._set_switch("otm_set_points", on)
 
     def points_info(self):
         """Whether matched points are on (otm_points_info)."""
-        on = C.c_int()
-        _check(lib().otm_points_info(self.h, C.byref(on)))
-        return bool(on.value)
+        return self._switch_info("otm_points_info")
 
     def points(self):
         """The last binary-level batch's matched points (otm_fetch_points): one
         _lib.POINT_DTYPE record per input point, in input order."""
-        n = C.c_int64()
-        _check(lib().otm_fetch_points(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=_lib.POINT_DTYPE)
-        _check(lib().otm_fetch_points(self.h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
-        return out
+        return self._fetch_per_point("otm_fetch_points", _lib.POINT_DTYPE)
 
     def points_device(self):
         """(device pointer, count) of the last batch's records in this GPU's HBM
         (otm_points_device; a one-device engine's, valid until its next batch)."""
-        p, n = C.c_void_p(), C.c_int64()
-        _check(lib().otm_points_device(self.h, C.byref(p), C.byref(n)))
-        return p.value or 0, n.value
+        return self._records_device("otm_points_device")
 
     def set_traversals(self, on):
         """The matched-route switch of this handle (otm_set_traversals; a multi-device
         engine passes it to every member, a clone inherits it when it is made)."""
-        _check(lib().otm_set_traversals(self.h, 1 if on else 0))
+        self._set_switch("otm_set_traversals", on)
 
     def traversals_info(self):
         """Whether the matched route is on (otm_traversals_info)."""
-        on = C.c_int()
-        _check(lib().otm_traversals_info(self.h, C.byref(on)))
-        return bool(on.value)
+        return self._switch_info("otm_traversals_info")
 
     def traversals(self):
         """The matched route of the handle's last binary-level batch
@@ -499,36 +512,26 @@ class Engine(object):
         """(records pointer, trav_off pointer, count) of the last batch's dense
         records in this GPU's HBM (otm_traversals_device; a one-device engine's,
         valid until its next batch)."""
-        p, o, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        _check(lib().otm_traversals_device(self.h, C.byref(p), C.byref(o), C.byref(n)))
-        return p.value or 0, o.value or 0, n.value
+        return self._records_device("otm_traversals_device", pointers=2)
 
     def set_scores(self, on):
         """The match-scores switch of this handle (otm_set_scores; a multi-device
         engine passes it to every member, a clone inherits it when it is made)."""
-        _check(lib().otm_set_scores(self.h, 1 if on else 0))
+        self._set_switch("otm_set_scores", on)
 
     def scores_info(self):
         """Whether match scores are on (otm_scores_info)."""
-        on = C.c_int()
-        _check(lib().otm_scores_info(self.h, C.byref(on)))
-        return bool(on.value)
+        return self._switch_info("otm_scores_info")
 
     def scores(self):
         """The last binary-level batch's match scores (otm_fetch_scores): one
         _lib.SCORE_DTYPE record per input point, in input order."""
-        n = C.c_int64()
-        _check(lib().otm_fetch_scores(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=_lib.SCORE_DTYPE)
-        _check(lib().otm_fetch_scores(self.h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
-        return out
+        return self._fetch_per_point("otm_fetch_scores", _lib.SCORE_DTYPE)
 
     def scores_device(self):
         """(device pointer, count) of the last batch's records in this GPU's HBM
         (otm_scores_device; a one-device engine's, valid until its next batch)."""
-        p, n = C.c_void_p(), C.c_int64()
-        _check(lib().otm_scores_device(self.h, C.byref(p), C.byref(n)))
-        return p.value or 0, n.value
+        return self._records_device("otm_scores_device")
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))
