@@ -796,7 +796,11 @@ int otm_get_spill_stats(otm_engine* eng, otm_spill_stats* out);
  * 10 ipos f32[P]; the batch inputs as the GPU request reader decoded them
  * (otm_report_batch; also a host batch of more than 2^18 points): 11 trace_off
  * i64[T+1], 12 lat f32[P], 13 lon f32[P], 14 time f64[P], 15 accuracy f32[P];
- * 16 chain_start u8[P], 17 is_col u8[P]. */
+ * 16 chain_start u8[P], 17 is_col u8[P]; the spatial work order, each valid
+ * only after a batch that ran the large plan (at least OTM_SMALL_POINTS
+ * points): 18 its items i32[columns] (the column points in walk order), 19
+ * the tile u16[P] (its Hilbert index; written for columns only), 20 the group
+ * starts i32[9]. */
 int otm_debug_fetch(otm_engine* eng, int what, void* dst, size_t bytes,
                     size_t* needed);
 int otm_kmax(void);

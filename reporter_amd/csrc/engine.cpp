@@ -1643,6 +1643,20 @@ int engine_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t*
     case 15: of(E->in_acc, Pn); break;
     case 16: of(E->chain_start, Pn); break;
     case 17: of(E->is_col, Pn); break;
+    // the spatial work order (valid only after a batch that ran the large
+    // plan): its items, every point's tile (columns' only are written), the
+    // group starts
+    case 18: {
+      int32_t total = 0;
+      if (E->ord_grp.p && E->ord_item.p) {
+        HIPCHK(hipMemcpyAsync(&total, E->ord_grp.p + ORDER_GROUPS, 4, hipMemcpyDeviceToHost, E->stream));
+        HIPCHK(hipStreamSynchronize(E->stream));
+      }
+      of(E->ord_item, total < 0 || (size_t)total > Pn ? 0 : (size_t)total);
+      break;
+    }
+    case 19: of(E->ord_tile, E->ord_tile.p ? Pn : 0); break;
+    case 20: of(E->ord_grp, E->ord_grp.p ? ORDER_GROUPS + 1 : 0); break;
     default: *err = "unknown debug buffer"; return OTM_EINVAL;
   }
   if (needed) *needed = n;

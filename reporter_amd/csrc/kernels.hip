@@ -355,23 +355,44 @@ __device__ __forceinline__ int tile_of(const DevGraph& g, float lat, float lon) 
 }
 
 // Wave-aggregated atomicAdd(&ctr[key], 1): one atomic per distinct key in
-// the wave; returns this lane's slot (consecutive points of a trace usually
-// share a tile, so a wave makes one to three atomics).  All 64 lanes call it.
-__device__ __forceinline__ int wave_agg_slot(int32_t* ctr, int key, bool active) {
+// the wave; returns this lane's slot.  64 consecutive points of a config-2
+// trace cross about 15 tiles, so the lanes are first matched by key in
+// registers (agg_match: one round per distinct key, no memory operation in
+// it); then every key's first lane adds its count in ONE atomic instruction,
+// and the wave waits for one round trip, not for one per key in turn.  All 64
+// lanes call these.
+struct AggMatch {
+  int leader;  // the first lane with this lane's key
+  int rank;    // lanes with the key below this one
+  int count;   // lanes with the key
+};
+__device__ __forceinline__ AggMatch agg_match(int key, bool active) {
   const int lane = threadIdx.x & 63;
   unsigned long long pending = __ballot(active);
-  int pos = 0;
+  AggMatch m{lane, 0, 0};
   while (pending) {
     const int leader = __ffsll((long long)pending) - 1;
     const int k = __shfl(key, leader, 64);
     const unsigned long long grp = __ballot(((pending >> lane) & 1ull) && key == k);
-    int base = 0;
-    if (lane == leader) base = atomicAdd(&ctr[k], (int)__popcll(grp));
-    base = __shfl(base, leader, 64);
-    if ((grp >> lane) & 1ull) pos = base + (int)__popcll(grp & ((1ull << lane) - 1ull));
+    if ((grp >> lane) & 1ull) {
+      m.leader = leader;
+      m.rank = (int)__popcll(grp & ((1ull << lane) - 1ull));
+      m.count = (int)__popcll(grp);
+    }
     pending &= ~grp;
   }
-  return pos;
+  return m;
+}
+__device__ __forceinline__ int wave_agg_slot(int32_t* ctr, int key, bool active) {
+  const AggMatch m = agg_match(key, active);
+  int base = 0;
+  if (active && m.leader == (int)(threadIdx.x & 63)) base = atomicAdd(&ctr[key], m.count);
+  return __shfl(base, m.leader, 64) + m.rank;
+}
+// ... counting only (K1): the atomics return nothing, so the wave does not wait at all
+__device__ __forceinline__ void wave_agg_count(int32_t* ctr, int key, bool active) {
+  const AggMatch m = agg_match(key, active);
+  if (active && m.leader == (int)(threadIdx.x & 63)) atomicAdd(&ctr[key], m.count);
 }
 
 // one block: exclusive scan of the tile counts (Hilbert order), cursors, and
@@ -551,7 +572,7 @@ __global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParam
         if (w.ord.tile_cnt) {  // spatial order: this column's tile, counted per wave
           const int tl = col ? tile_of(g, sLat[pl], sLon[pl]) : 0;
           if (col) w.ord.tile[a + pl] = (uint16_t)tl;
-          (void)wave_agg_slot(w.ord.tile_cnt, tl, col);
+          wave_agg_count(w.ord.tile_cnt, tl, col);
         }
       }
       __syncthreads();

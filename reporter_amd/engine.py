@@ -574,7 +574,9 @@ class Engine(object):
               # the last batch's inputs as the GPU request reader decoded them
               "in_trace_off": (11, np.int64), "in_lat": (12, np.float32), "in_lon": (13, np.float32),
               "in_time": (14, np.float64), "in_acc": (15, np.float32),
-              "chain_start": (16, np.uint8), "is_col": (17, np.uint8)}
+              "chain_start": (16, np.uint8), "is_col": (17, np.uint8),
+              # the spatial work order (after a batch of at least OTM_SMALL_POINTS points)
+              "order_item": (18, np.int32), "order_tile": (19, np.uint16), "order_grp": (20, np.int32)}
 
     def debug(self, name):
         what, dt = self._DEBUG[name]
