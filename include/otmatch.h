@@ -533,6 +533,61 @@ int otm_scores_info(const otm_engine* eng, int* on);
 int otm_fetch_scores(otm_engine* eng, otm_point_score* dst, int64_t cap, int64_t* n_points);
 int otm_scores_device(otm_engine* eng, const void** dev, int64_t* n_points);
 
+/* Matched shape (extension, DESIGN.md §3 rule 7f): the geometry of the route
+ * each trace of the last binary-level batch was matched to -- per trace one
+ * vertex list in microdegrees, one span of it per traversal, and one polyline6
+ * string, all made on the GPU (k_shape) from the trace's rule-7d records and
+ * the graph's shape points.  Off by default, per handle: with the switch off
+ * nothing is launched or allocated; with it on, a binary-level match also runs
+ * k_traversals (whether or not otm_set_traversals is on: that call keeps its
+ * own switch), and everything else happens at the first size, fetch or device
+ * call for the batch.  A clone inherits its parent's value when it is made; a
+ * multi-device engine passes the call to every member.
+ *   Per trace, in record order: a record with OTM_TV_CHAIN_START emits the
+ *   point of its edge at begin_offset (rule 7c's coordinate); a record without
+ *   it emits no first vertex, the previous record's last vertex is its first.
+ *   Then the edge's shape points 1..m-1 whose cumulative length lies strictly
+ *   between begin_offset and end_offset, then always the point at end_offset.
+ *   lat_e6 = (int32)rint(lat * 1e6), lon_e6 alike (round half even).
+ *   A span's begin_vertex / end_vertex are trace-relative indices of the
+ *   record's first and last vertex: end_vertex > begin_vertex; inside a chain
+ *   begin_vertex equals the previous end_vertex, a chain start has the previous
+ *   end_vertex + 1 (0 on the trace's first record).
+ *   The polyline is the usual polyline6 over the whole vertex list (lat, then
+ *   lon; deltas from (0, 0); zigzag; 5-bit groups low first; + 63), without a
+ *   terminator; a chain break is a large delta.  A value takes at most 6 chars.
+ *   A trace without records has no vertices and an empty string.
+ * Validity is the matched route's own: only the three binary-level calls leave
+ * a shape; any batch in the handle's buffers ends the last one's. */
+typedef struct otm_shape_vertex { int32_t lat_e6, lon_e6; } otm_shape_vertex;        /* 8 bytes */
+typedef struct otm_shape_span { int32_t begin_vertex, end_vertex; } otm_shape_span; /* 8 bytes, one per traversal,
+                                                                                        in otm_fetch_traversals' order */
+typedef struct otm_shape_sizes { int64_t n_traces, n_traversals, n_vertices, n_bytes; } otm_shape_sizes;
+typedef struct otm_shape_out { /* any pointer may be NULL: that part is not copied */
+  otm_shape_vertex* vertices; int64_t vertices_cap; int64_t* vtx_off;  /* [n_traces + 1] */
+  otm_shape_span* spans;      int64_t spans_cap;    int64_t* trav_off; /* [n_traces + 1] */
+  char* polyline;             int64_t polyline_cap; int64_t* poly_off; /* [n_traces + 1] */
+} otm_shape_out;
+/* otm_set_shape: the switch (on != 0).  otm_shape_info: its value.
+ * otm_shape_size: the counts of the batch the fetch answers for.
+ * otm_fetch_shape answers for the handle's last otm_match_soa,
+ * otm_match_compact or otm_match_device batch, any number of times with the
+ * same bytes: trace t's vertices at [vtx_off[t], vtx_off[t + 1]), its spans at
+ * [trav_off[t], trav_off[t + 1]) (otm_fetch_traversals' own offsets), its
+ * string at [poly_off[t], poly_off[t + 1]).  On a multi-device engine the
+ * members' arrays are joined in the batch's trace order (only the three offset
+ * arrays are rebased).  otm_shape_device: the device arrays of a one-device
+ * engine (valid until its next batch), ordered behind the engine's stream; the
+ * caps of *dev are set to the counts.  OTM_EINVAL (message in otm_last_error):
+ * a NULL engine or argument, a call with the switch off or with no
+ * binary-level batch with it on as the handle's last batch, a cap below its
+ * count, otm_shape_device on a multi-device handle. */
+int otm_set_shape(otm_engine* eng, int on);
+int otm_shape_info(const otm_engine* eng, int* on);
+int otm_shape_size(otm_engine* eng, otm_shape_sizes* out);
+int otm_fetch_shape(otm_engine* eng, const otm_shape_out* dst);
+int otm_shape_device(otm_engine* eng, otm_shape_out* dev, otm_shape_sizes* n);
+
 /* Per-segment speed histogram, accumulated on the device by every match
  * call: counts u32[n_segments * nbins], bin = floor(kph / bin_kph) clamped to
  * nbins-1, one count per datastore report.  The buffer is CALLER-owned device

@@ -171,6 +171,22 @@ class PointScore(C.Structure):
 
 SC_SCORED, SC_CHAIN_START, SC_CHAIN_END, SC_ALONE, SC_TIE = 1, 2, 4, 8, 16
 
+# otm_shape_vertex, otm_shape_span (include/otmatch.h): 8 bytes each
+SHAPE_VERTEX_DTYPE = np.dtype([("lat_e6", "<i4"), ("lon_e6", "<i4")])
+SHAPE_SPAN_DTYPE = np.dtype([("begin_vertex", "<i4"), ("end_vertex", "<i4")])
+
+
+class ShapeSizes(C.Structure):
+    _fields_ = [("n_traces", C.c_int64), ("n_traversals", C.c_int64), ("n_vertices", C.c_int64),
+                ("n_bytes", C.c_int64)]
+
+
+class ShapeOut(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("vertices_cap", C.c_int64), ("vtx_off", C.c_void_p),
+                ("spans", C.c_void_p), ("spans_cap", C.c_int64), ("trav_off", C.c_void_p),
+                ("polyline", C.c_void_p), ("polyline_cap", C.c_int64), ("poly_off", C.c_void_p)]
+
+
 SEG_START_VALID, SEG_END_VALID, SEG_INTERNAL, SEG_START_INT, SEG_END_INT = 1, 2, 4, 8, 16
 REP_T1_INT, REP_T0_INT = 1, 2
 REP_T1_INT_MINUS1 = REP_T1_INT
@@ -201,6 +217,11 @@ def _declare(L):
         "otm_scores_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "otm_fetch_scores": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
         "otm_scores_device": (C.c_int, [vp, pp, C.POINTER(i64)]),
+        "otm_set_shape": (C.c_int, [vp, C.c_int]),
+        "otm_shape_info": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "otm_shape_size": (C.c_int, [vp, C.POINTER(ShapeSizes)]),
+        "otm_fetch_shape": (C.c_int, [vp, C.POINTER(ShapeOut)]),
+        "otm_shape_device": (C.c_int, [vp, C.POINTER(ShapeOut), C.POINTER(ShapeSizes)]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

@@ -2261,6 +2261,9 @@ int otm_queue_info(const otm_engine* E, float* kph) {
 static_assert(sizeof(otm_matched_point) == 40 && alignof(otm_matched_point) == 8, "matched point record");
 static_assert(sizeof(otm_traversal) == 56 && alignof(otm_traversal) == 8, "traversal record");
 static_assert(sizeof(otm_point_score) == 32 && alignof(otm_point_score) == 4, "point score record");
+static_assert(sizeof(otm_shape_vertex) == 8 && sizeof(otm_shape_span) == 8 && sizeof(otm_shape_sizes) == 32 &&
+                  sizeof(otm_shape_out) == 72,
+              "matched shape records");
 
 }  // extern "C"
 
@@ -2406,6 +2409,91 @@ int otm_traversals_device(otm_engine* E, const void** recs, const int64_t** trav
     const int rc = otm::engine_traversals_dense(E, err);
     if (!rc && trav_off) *trav_off = E->tv_off.p;
     return rc;
+  });
+}
+
+// The matched shape (rule 7f) has three arrays and three offset arrays; its first size, fetch or
+// device call of a batch makes them (engine_shape_make).  A multi-device handle answers out of its
+// joined arrays (group.cpp).
+int otm_set_shape(otm_engine* E, int on) { return records_set(E, &otm_engine::shape, on); }
+int otm_shape_info(const otm_engine* E, int* on) { return records_info(E, &otm_engine::shape, on); }
+
+// the joined arrays' counts, or the reason there are none (under G->mu)
+static int group_shape_sizes(const otm_engine* G, otm_shape_sizes* z) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<otm_shape_vertex>;
+  if (!G->shape.on) return fail(OTM_EINVAL, d.off);
+  if (G->shape.joined_n < 0) return fail(OTM_EINVAL, d.none);
+  *z = otm_shape_sizes{(int64_t)G->g_sh_vtx_off.size() - 1, (int64_t)G->g_sh_span.size(), G->shape.joined_n,
+                       (int64_t)G->g_sh_poly.size()};
+  return OTM_OK;
+}
+
+int otm_shape_size(otm_engine* E, otm_shape_sizes* out) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<otm_shape_vertex>;
+  if (!E || !out) return fail(OTM_EINVAL, d.dev_null);
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(E->mu);
+    otm_shape_sizes z;
+    if (!E->members.empty()) {
+      if (const int rc = group_shape_sizes(E, &z)) return rc;
+    } else {
+      if (E->device >= 0) (void)hipSetDevice(E->device);
+      std::string err;
+      if (const int rc = otm::engine_shape_make(E, &z, &err)) return fail(rc, err);
+    }
+    *out = z;
+    return (int)OTM_OK;
+  });
+}
+
+int otm_fetch_shape(otm_engine* E, const otm_shape_out* dst) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<otm_shape_vertex>;
+  if (!E || !dst) return fail(OTM_EINVAL, d.dev_null);
+  if (dst->vertices_cap < 0 || dst->spans_cap < 0 || dst->polyline_cap < 0 || (!dst->vertices && dst->vertices_cap) ||
+      (!dst->spans && dst->spans_cap) || (!dst->polyline && dst->polyline_cap))
+    return fail(OTM_EINVAL, d.dst_null);
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (E->members.empty()) {
+      if (E->device >= 0) (void)hipSetDevice(E->device);
+      std::string err;
+      const int rc = otm::engine_fetch_shape(E, dst, &err);
+      return rc ? fail(rc, err) : (int)OTM_OK;
+    }
+    otm_shape_sizes z;
+    if (const int rc = group_shape_sizes(E, &z)) return rc;
+    if ((dst->vertices && dst->vertices_cap < z.n_vertices) || (dst->spans && dst->spans_cap < z.n_traversals) ||
+        (dst->polyline && dst->polyline_cap < z.n_bytes))
+      return fail(OTM_EINVAL, d.cap);
+    const size_t ob = ((size_t)z.n_traces + 1) * sizeof(int64_t);
+    if (dst->vtx_off) std::memcpy(dst->vtx_off, E->g_sh_vtx_off.data(), ob);
+    if (dst->trav_off) std::memcpy(dst->trav_off, E->g_sh_trav_off.data(), ob);
+    if (dst->poly_off) std::memcpy(dst->poly_off, E->g_sh_poly_off.data(), ob);
+    if (dst->vertices && z.n_vertices)
+      std::memcpy(dst->vertices, E->shape.joined.data(), (size_t)z.n_vertices * sizeof(otm_shape_vertex));
+    if (dst->spans && z.n_traversals)
+      std::memcpy(dst->spans, E->g_sh_span.data(), (size_t)z.n_traversals * sizeof(otm_shape_span));
+    if (dst->polyline && z.n_bytes) std::memcpy(dst->polyline, E->g_sh_poly.data(), (size_t)z.n_bytes);
+    return (int)OTM_OK;
+  });
+}
+
+int otm_shape_device(otm_engine* E, otm_shape_out* dev, otm_shape_sizes* n) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<otm_shape_vertex>;
+  if (!E || !dev) return fail(OTM_EINVAL, d.dev_null);
+  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    otm_shape_sizes z;
+    std::string err;
+    if (const int rc = otm::engine_shape_make(E, &z, &err)) return fail(rc, err);
+    const size_t T1 = (size_t)z.n_traces + 1;
+    *dev = otm_shape_out{z.n_vertices ? E->shape.dev.p : nullptr, z.n_vertices,   E->sh_off.p,
+                         z.n_traversals ? E->sh_span.p : nullptr, z.n_traversals, E->tv_off.p,
+                         z.n_bytes ? E->sh_poly.p : nullptr,      z.n_bytes,      E->sh_off.p + T1};
+    if (n) *n = z;
+    return (int)OTM_OK;
   });
 }
 

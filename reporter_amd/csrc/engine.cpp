@@ -389,6 +389,7 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->points.on = P->points.on;
   C->route.on = P->route.on;
   C->scores.on = P->scores.on;
+  C->shape.on = P->shape.on;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -918,12 +919,15 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   }
   // K7d (DESIGN.md §3 rule 7d): likewise, and only for a binary-level batch.  Every attempt writes
   // each trace's whole count and region; the dense form is made at the first fetch.
-  if (records_wanted(E, E->route)) {
+  // The matched shape (rule 7f) is made from these records at its first fetch: its switch runs K7d too.
+  const bool for_route = records_wanted(E, E->route), for_shape = records_wanted(E, E->shape);
+  if (for_route || for_shape) {
     DevTrav tv{};
     TRY(bind_trav(E, NT, NP, tv, err));
     HIPCHK(hipMemsetAsync(tv.cnt + NT, 0, sizeof *tv.cnt, s));
     launch_traversals(E->g, b, w, o, tv, s);
-    E->tv_T = NT;
+    if (for_route) E->tv_T = NT;
+    if (for_shape) E->sh_T = NT;
   }
   launch_report(b, E->drc, w, o, s, mk);
   HIPCHK(hipGetLastError());
@@ -1679,7 +1683,10 @@ void end_records(otm_engine* E, RecEvent event) {
   end_if(E->points, event);
   end_if(E->route, event);
   end_if(E->scores, event);
-  if (kRecDesc<otm_traversal>.ends & event) E->tv_T = -1;  // (the regions its dense form is made from)
+  end_if(E->shape, event);
+  // (the regions the route's dense form and the shape are made from, and their scanned counts)
+  if (kRecDesc<otm_traversal>.ends & event) E->tv_T = E->tv_off_T = -1;
+  if (kRecDesc<otm_shape_vertex>.ends & event) E->sh_T = -1;
 }
 
 template <class Rec>
@@ -1714,6 +1721,24 @@ template int engine_fetch_records(otm_engine*, BatchRecords<otm_traversal>&, otm
 template int engine_fetch_records(otm_engine*, BatchRecords<otm_point_score>&, otm_point_score*, int64_t, int64_t*,
                                   std::string*);
 
+// The dense traversal offsets of the last batch that ran k_traversals (NT its trace count): the
+// exclusive scan of the per-trace counts in E->tv_off, its pinned copy in E->h_tv_off.  Made once per
+// batch, by the matched route's or the matched shape's first call, whichever comes first.  wait false:
+// the copy is only enqueued; the caller waits for the stream itself and then sets E->tv_off_T.
+static int trav_offsets(otm_engine* E, int32_t NT, std::string* err, bool wait = true) {
+  if (E->tv_off_T == NT) return OTM_OK;
+  hipStream_t s = E->stream;
+  TRY(E->tv_off.ensure((size_t)NT + 1, err));
+  TRY(E->h_tv_off.ensure((size_t)NT + 1, err));
+  HIPCHK(hipMemcpyAsync(E->tv_off.p, E->tv_cnt.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToDevice, s));
+  if (NT) scan_i64(E->tv_off.p, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+  HIPCHK(hipMemcpyAsync(E->h_tv_off.p, E->tv_off.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToHost, s));
+  if (!wait) return OTM_OK;
+  HIPCHK(wait_batch(E, s, E->last_P));
+  E->tv_off_T = NT;
+  return OTM_OK;
+}
+
 int engine_traversals_dense(otm_engine* E, std::string* err) {
   if (!E->route.on) {
     *err = kRecDesc<otm_traversal>.off;
@@ -1728,12 +1753,7 @@ int engine_traversals_dense(otm_engine* E, std::string* err) {
   const int32_t NT = E->tv_T;
   // dense offsets: the exclusive scan of the per-trace counts, then one copy
   // pass out of the per-trace regions
-  TRY(E->tv_off.ensure((size_t)NT + 1, err));
-  TRY(E->h_tv_off.ensure((size_t)NT + 1, err));
-  HIPCHK(hipMemcpyAsync(E->tv_off.p, E->tv_cnt.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToDevice, s));
-  if (NT) scan_i64(E->tv_off.p, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
-  HIPCHK(hipMemcpyAsync(E->h_tv_off.p, E->tv_off.p, ((size_t)NT + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(wait_batch(E, s, E->last_P));
+  TRY(trav_offsets(E, NT, err));
   const int64_t n = E->h_tv_off.p[NT];
   TRY(E->route.dev.ensure((size_t)n + 1, err));
   if (NT && n) {
@@ -1749,6 +1769,94 @@ int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int6
   TRY(engine_traversals_dense(E, err));
   if (trav_off) std::memcpy(trav_off, E->h_tv_off.p, ((size_t)E->tv_T + 1) * 8);
   return engine_fetch_records(E, E->route, dst, cap, n, err);
+}
+
+int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err) {
+  constexpr const RecDesc& d = kRecDesc<otm_shape_vertex>;
+  if (!E->shape.on) {
+    *err = d.off;
+    return OTM_EINVAL;
+  }
+  if (E->sh_T < 0) {
+    *err = d.none;
+    return OTM_EINVAL;
+  }
+  const int32_t NT = E->sh_T;
+  const size_t T1 = (size_t)NT + 1;
+  if (E->shape.n < 0) {  // (else: made by an earlier call for this batch)
+    hipStream_t s = E->stream;
+    TRY(E->sh_off.ensure(2 * T1, err));
+    TRY(E->h_sh_off.ensure(2 * T1, err));
+    TRY(trav_offsets(E, NT, err, false));  // (its copy comes home with the wait below)
+    DevTrav tv{E->tv_rec.p, E->tv_cnt.p};
+    DevShape sh{};
+    sh.trav_off = E->tv_off.p;
+    sh.vtx_off = E->sh_off.p;
+    sh.poly_off = E->sh_off.p + T1;
+    // the count pass, the two scans over traces, one copy of both offset arrays and the call's one wait
+    HIPCHK(hipMemsetAsync(E->sh_off.p, 0, 2 * T1 * 8, s));
+    if (NT) {
+      launch_shape(E->g, NT, E->seg_ub.p, tv, sh, false, s);
+      HIPCHK(hipGetLastError());
+      scan_i64(sh.vtx_off, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+      scan_i64(sh.poly_off, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    }
+    HIPCHK(hipMemcpyAsync(E->h_sh_off.p, E->sh_off.p, 2 * T1 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_batch(E, s, E->last_P));
+    E->tv_off_T = NT;
+    const int64_t n_trav = E->h_tv_off.p[NT];
+    const int64_t nv = E->h_sh_off.p[NT], nb = E->h_sh_off.p[T1 + NT];
+    TRY(E->shape.dev.ensure((size_t)nv + 1, err));
+    TRY(E->sh_span.ensure((size_t)n_trav + 1, err));
+    TRY(E->sh_poly.ensure((size_t)nb + 1, err));
+    if (NT && n_trav) {
+      sh.vtx = E->shape.dev.p;
+      sh.span = E->sh_span.p;
+      sh.poly = E->sh_poly.p;
+      launch_shape(E->g, NT, E->seg_ub.p, tv, sh, true, s);
+      HIPCHK(hipGetLastError());
+    }
+    E->sh_bytes = nb;
+    E->shape.n = nv;
+  }
+  if (sz) *sz = otm_shape_sizes{NT, E->h_tv_off.p[NT], E->shape.n, E->sh_bytes};
+  return OTM_OK;
+}
+
+int engine_fetch_shape(otm_engine* E, const otm_shape_out* dst, std::string* err) {
+  otm_shape_sizes z;
+  TRY(engine_shape_make(E, &z, err));
+  if ((dst->vertices && dst->vertices_cap < z.n_vertices) || (dst->spans && dst->spans_cap < z.n_traversals) ||
+      (dst->polyline && dst->polyline_cap < z.n_bytes)) {
+    *err = kRecDesc<otm_shape_vertex>.cap;
+    return OTM_EINVAL;
+  }
+  const size_t T1 = (size_t)z.n_traces + 1;
+  if (dst->vtx_off) std::memcpy(dst->vtx_off, E->h_sh_off.p, T1 * 8);
+  if (dst->poly_off) std::memcpy(dst->poly_off, E->h_sh_off.p + T1, T1 * 8);
+  if (dst->trav_off) std::memcpy(dst->trav_off, E->h_tv_off.p, T1 * 8);
+  // the three arrays: queued one behind the other, one wait
+  const size_t vb = dst->vertices ? (size_t)z.n_vertices * sizeof(otm_shape_vertex) : 0;
+  const size_t sb = dst->spans ? (size_t)z.n_traversals * sizeof(otm_shape_span) : 0;
+  const size_t pb = dst->polyline ? (size_t)z.n_bytes : 0;
+  if (!(vb || sb || pb)) return OTM_OK;
+  if (vb) {
+    TRY(E->shape.pin.ensure((size_t)z.n_vertices, err));
+    HIPCHK(big_copy(E->shape.pin.p, E->shape.dev.p, vb, hipMemcpyDeviceToHost, E->stream));
+  }
+  if (sb) {
+    TRY(E->h_sh_span.ensure((size_t)z.n_traversals, err));
+    HIPCHK(big_copy(E->h_sh_span.p, E->sh_span.p, sb, hipMemcpyDeviceToHost, E->stream));
+  }
+  if (pb) {
+    TRY(E->h_sh_poly.ensure(pb, err));
+    HIPCHK(big_copy(E->h_sh_poly.p, E->sh_poly.p, pb, hipMemcpyDeviceToHost, E->stream));
+  }
+  HIPCHK(wait_batch(E, E->stream, z.n_vertices));
+  if (vb) std::memcpy(dst->vertices, E->shape.pin.p, vb);
+  if (sb) std::memcpy(dst->spans, E->h_sh_span.p, sb);
+  if (pb) std::memcpy(dst->polyline, E->h_sh_poly.p, pb);
+  return OTM_OK;
 }
 
 int engine_spill_stats(otm_engine* E, otm_spill_stats* out) {

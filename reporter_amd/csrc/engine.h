@@ -43,7 +43,7 @@ struct H2DOrder {
   bool own_queue = false;
 };
 // ---- Optional per-batch outputs: matched points (rule 7c), the matched route
-// (7d), match scores (7e).  Each is a switch on the handle and one array of
+// (7d), match scores (7e), the matched shape (7f).  Each is a switch on the handle and one array of
 // records that the last batch left, fetched any number of times until an
 // event ends them.
 //
@@ -64,7 +64,7 @@ struct RecDesc {
 };
 template <class Rec>
 inline constexpr RecDesc kRecDesc{};
-// The validity table.  The three rules differ, as otmatch.h documents them:
+// The validity table.  The rules differ, as otmatch.h documents them:
 //  - matched points came first and any kind of batch writes them: records stand until the next batch
 //    with its outputs in this handle's buffers replaces them (REC_BATCH_OUTPUTS), so a batch that fails
 //    before that point, and a JSON call, leave the last ones fetchable;
@@ -88,6 +88,13 @@ inline constexpr RecDesc kRecDesc<otm_point_score>{
     "match scores are off (otm_set_scores)", "no batch has run with match scores on",
     "match scores: cap below the batch's point count", "match scores: dst is NULL with cap != 0",
     "engine or dev is NULL", true, REC_BATCH_BEGINS | REC_BATCH_FAILED | REC_OTHER_CALL};
+//  - the matched shape (rule 7f; its records are the vertices) is made from the route's regions, so it
+//    is binary-only and ends with them.
+template <>
+inline constexpr RecDesc kRecDesc<otm_shape_vertex>{
+    "the matched shape is off (otm_set_shape)", "no batch has run with the matched shape on",
+    "matched shape: a cap is below its count", "matched shape: an array is NULL with cap != 0",
+    "engine or an argument is NULL", true, kRecDesc<otm_traversal>.ends};
 
 template <class Rec>
 struct BatchRecords {
@@ -344,9 +351,10 @@ struct otm_engine {
   // the matched route: route.dev is the dense form, made at the first fetch or device call of a batch
   // (route.n: -1 until then).  tv_rec / tv_cnt: DevTrav's regions and counts as the batch wrote them
   // (tv_T its trace count, -1: no batch left any); tv_off / h_tv_off: the counts' scan and its pinned
-  // copy; g_tv_off: a multi-device engine's joined offsets
+  // copy, made once per batch by the route's or the shape's first call (tv_off_T: the trace count they
+  // were made for, -1: not yet); g_tv_off: a multi-device engine's joined offsets
   otm::BatchRecords<otm_traversal> route;
-  int32_t tv_T = -1;
+  int32_t tv_T = -1, tv_off_T = -1;
   otm::DevBuf<otm_traversal> tv_rec;
   otm::DevBuf<int64_t> tv_cnt, tv_off;
   otm::PinBuf<int64_t> h_tv_off;
@@ -356,6 +364,24 @@ struct otm_engine {
   otm::BatchRecords<otm_point_score> scores;
   otm::DevBuf<float> sc_alpha, sc_alpha_x;
   otm::DevBuf<int32_t> sc_rej;
+  // the matched shape (k_shape), made from tv_rec / tv_cnt at the first size, fetch or device call of a
+  // batch: shape.dev the vertices (shape.n: -1 until then), sh_span one span per traversal, sh_poly the
+  // polyline chars (sh_bytes of them).  sh_T: the trace count of the last batch that ran k_traversals for
+  // it (-1: none).  sh_off: vtx_off[sh_T + 1] then poly_off[sh_T + 1] in one array, h_sh_off its pinned
+  // copy; h_sh_span / h_sh_poly: the fetch's staging; g_sh_*: a multi-device engine's joined arrays
+  // (its vertices: shape.joined)
+  otm::BatchRecords<otm_shape_vertex> shape;
+  int32_t sh_T = -1;
+  int64_t sh_bytes = 0;
+  otm::DevBuf<otm_shape_span> sh_span;
+  otm::DevBuf<char> sh_poly;
+  otm::DevBuf<int64_t> sh_off;
+  otm::PinBuf<int64_t> h_sh_off;
+  otm::PinBuf<otm_shape_span> h_sh_span;
+  otm::PinBuf<char> h_sh_poly;
+  std::vector<otm_shape_span> g_sh_span;
+  std::vector<char> g_sh_poly;
+  std::vector<int64_t> g_sh_vtx_off, g_sh_trav_off, g_sh_poly_off;
 };
 
 namespace otm {
@@ -434,6 +460,13 @@ int engine_traversals_dense(otm_engine* E, std::string* err);
 // ... then engine_fetch_records, and the tv_T + 1 offsets to trav_off (may be null)
 int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
                             std::string* err);
+// the matched shape's preparation (rule 7f): once per batch the dense traversal offsets, k_shape's
+// count pass, the two scans, one copy of the offsets and one wait, then the write pass (E->shape.dev,
+// E->sh_span, E->sh_poly, E->sh_off; E->shape.n, E->sh_bytes).  *sz (may be null): the four counts.
+// OTM_EINVAL when the switch is off or no batch ran with it on
+int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err);
+// ... then copies the parts of dst that are not null; OTM_EINVAL also when a cap is below its count
+int engine_fetch_shape(otm_engine* E, const otm_shape_out* dst, std::string* err);
 int engine_counters(otm_engine* E, otm_work_counters* out);
 // report() on the GPU over caller-supplied typed segments (otm_report_segments_device):
 // per trace t its points' times [trace_off[t], trace_off[t+1]) and segments

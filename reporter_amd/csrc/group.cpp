@@ -115,6 +115,11 @@ struct MemberOut {
   std::vector<otm_point_score> sc;     // (with the match-scores switch on, a binary-level batch)
   std::vector<otm_traversal> tv;       // (with the matched-route switch on) dense records,
   std::vector<int64_t> tv_off;         // member trace i's at [tv_off[i], tv_off[i + 1])
+  // (with the matched-shape switch on) the member's three arrays and their offsets
+  std::vector<otm_shape_vertex> sh_vtx;
+  std::vector<otm_shape_span> sh_span;
+  std::vector<char> sh_poly;
+  std::vector<int64_t> sh_vtx_off, sh_trav_off, sh_poly_off;
   int rc = 0;
   std::string err;
 };
@@ -134,6 +139,7 @@ void run_member(otm_engine* M, MemberOut& o) {
     M->points.on = M->group->points.on;
     M->route.on = M->group->route.on;
     M->scores.on = M->group->scores.on;
+    M->shape.on = M->group->shape.on;
     M->binary_batch = M->group->binary_batch;
   }
   otm_results r;
@@ -159,6 +165,21 @@ void run_member(otm_engine* M, MemberOut& o) {
     o.rc = engine_fetch_traversals(M, nullptr, 0, o.tv_off.data(), &n, &o.err);
     o.tv.resize((size_t)n);
     if (!o.rc && n) o.rc = engine_fetch_traversals(M, o.tv.data(), n, nullptr, &n, &o.err);
+  }
+  if (records_wanted(M, M->shape) && !o.rc) {
+    otm_shape_sizes z{};
+    o.rc = engine_shape_make(M, &z, &o.err);
+    if (o.rc) return;
+    o.sh_vtx.resize((size_t)z.n_vertices);
+    o.sh_span.resize((size_t)z.n_traversals);
+    o.sh_poly.resize((size_t)z.n_bytes);
+    o.sh_vtx_off.resize((size_t)z.n_traces + 1);
+    o.sh_trav_off.resize((size_t)z.n_traces + 1);
+    o.sh_poly_off.resize((size_t)z.n_traces + 1);
+    const otm_shape_out dst{z.n_vertices ? o.sh_vtx.data() : nullptr,    z.n_vertices,   o.sh_vtx_off.data(),
+                            z.n_traversals ? o.sh_span.data() : nullptr, z.n_traversals, o.sh_trav_off.data(),
+                            z.n_bytes ? o.sh_poly.data() : nullptr,      z.n_bytes,      o.sh_poly_off.data()};
+    o.rc = engine_fetch_shape(M, &dst, &o.err);
   }
 }
 
@@ -276,6 +297,29 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
       G->g_tv_off[(size_t)t + 1] = (int64_t)g_tv.size();
     }
     G->route.joined_n = (int64_t)g_tv.size();
+  }
+  // the members' matched shapes, likewise (vertex indices are trace-relative: only the offsets are rebased)
+  if (records_wanted(G, G->shape)) {
+    std::vector<otm_shape_vertex>& vtx = G->shape.joined;
+    vtx.clear();
+    G->g_sh_span.clear();
+    G->g_sh_poly.clear();
+    G->g_sh_vtx_off.assign((size_t)nt + 1, 0);
+    G->g_sh_trav_off.assign((size_t)nt + 1, 0);
+    G->g_sh_poly_off.assign((size_t)nt + 1, 0);
+    for (int32_t t = 0; t < nt; ++t) {
+      const MemberOut& o = mo[(size_t)mem[(size_t)t]];
+      const size_t i = (size_t)pos[(size_t)t];
+      vtx.insert(vtx.end(), o.sh_vtx.begin() + o.sh_vtx_off[i], o.sh_vtx.begin() + o.sh_vtx_off[i + 1]);
+      G->g_sh_span.insert(G->g_sh_span.end(), o.sh_span.begin() + o.sh_trav_off[i],
+                          o.sh_span.begin() + o.sh_trav_off[i + 1]);
+      G->g_sh_poly.insert(G->g_sh_poly.end(), o.sh_poly.begin() + o.sh_poly_off[i],
+                          o.sh_poly.begin() + o.sh_poly_off[i + 1]);
+      G->g_sh_vtx_off[(size_t)t + 1] = (int64_t)vtx.size();
+      G->g_sh_trav_off[(size_t)t + 1] = (int64_t)G->g_sh_span.size();
+      G->g_sh_poly_off[(size_t)t + 1] = (int64_t)G->g_sh_poly.size();
+    }
+    G->shape.joined_n = (int64_t)vtx.size();
   }
   out->n_traces = nt;
   out->n_segments = (int32_t)G->g_segs.size();

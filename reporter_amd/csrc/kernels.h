@@ -437,6 +437,19 @@ struct DevTrav {
   int64_t* cnt;        // [T+1] records per trace (cnt[T] = 0: scanned into trav_off at the fetch)
 };
 
+// The matched shape's arrays (DESIGN.md §3 rule 7f; made at the first size,
+// fetch or device call of a batch).  The count pass leaves each trace's vertex
+// and byte counts in vtx_off / poly_off, which the host scans in place; the
+// write pass reads them as offsets.
+struct DevShape {
+  const int64_t* trav_off;  // [T+1] the dense traversal offsets (the scan of DevTrav::cnt): where the spans go
+  int64_t* vtx_off;         // [T+1] counts, then offsets (element T: 0, then the total)
+  int64_t* poly_off;        // [T+1] likewise, in bytes
+  otm_shape_vertex* vtx;    // [vtx_off[T]]    (write pass only)
+  otm_shape_span* span;     // [trav_off[T]]
+  char* poly;               // [poly_off[T]]
+};
+
 // Per-kernel timing (otm_get_kernel_ms): when ev != nullptr the launchers
 // record ev[2k] just before and ev[2k+1] just after kernel k, on the launch
 // stream.  Order and names: kKernelNames in kernels.hip.
@@ -523,6 +536,12 @@ struct DevScores {
   int32_t* rej_n;        // [1] their count (zeroed by the launch)
 };
 void launch_scores(const DevBatch& b, DevWork& w, const DevScores& sc, hipStream_t s);
+// K7f: the matched shape of the traces' records as k_traversals left them in
+// their regions (DESIGN.md §3 rule 7f).  write false: the per-trace vertex and
+// byte counts into sh.vtx_off / sh.poly_off; write true: vertices, spans and
+// polyline chars at the scanned offsets.  Fetch time only; no timing slot.
+void launch_shape(const DevGraph& g, int32_t n_traces, const int64_t* seg_base, const DevTrav& tv, const DevShape& sh,
+                  bool write, hipStream_t s);
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);

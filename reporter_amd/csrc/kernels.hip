@@ -5590,6 +5590,168 @@ __global__ __launch_bounds__(TB) void k_scores(DevBatch b, DevWork w, DevScores 
   }
 }
 
+// ============================================================== K7f matched shape
+// (after K7e, for the same reason: the code object lays the timed kernels out as it did without it)
+// Rule 7c's Coordinate at `off` on an edge with shape points s0 .. s0 + nsh: k_points' expression,
+// operand for operand (the lowest shape segment with off <= cum[s + 1], t and the point in double).  Kept apart
+// from k_points: with one function called from both, k_points' assembly came out different.
+__device__ __forceinline__ void shape_coord(const DevGraph& g, int32_t s0, int32_t nsh, float off, double& lat,
+                                            double& lon) {
+  lat = lon = 0.0;
+  if (nsh < 1) return;  // (every edge of a graph file has a shape segment)
+  int sg = 0;
+  float c1 = g.s_cum[s0 + 1];
+  while (sg + 1 < nsh && !(off <= c1)) {
+    ++sg;
+    c1 = g.s_cum[s0 + sg + 1];
+  }
+  const double c0d = (double)g.s_cum[s0 + sg], c1d = (double)c1;
+  const double tt = c1d == c0d ? 0.0 : ((double)off - c0d) / (c1d - c0d);
+  const double la0 = (double)g.s_lat[s0 + sg], lo0 = (double)g.s_lon[s0 + sg];
+  lat = la0 + tt * ((double)g.s_lat[s0 + sg + 1] - la0);
+  lon = lo0 + tt * ((double)g.s_lon[s0 + sg + 1] - lo0);
+}
+// one polyline value's chars (n of them: 1 + floor(log2(v | 1)) / 5) at d
+__device__ __forceinline__ char* shape_put(char* d, uint32_t v, int n) {
+  for (int i = 0; i < n; ++i) {
+    const uint32_t q = v & 31u;
+    v >>= 5;
+    *d++ = (char)((q | (i + 1 < n ? 0x20u : 0u)) + 63u);
+  }
+  return d;
+}
+
+// One wavefront per trace, over its rule-7d records as k_traversals left them
+// in the trace's region, 64 at a time.  A record lane reads its record's edge,
+// flags and two offsets and the edge's shape range, finds the interior shape
+// points (those with begin_offset < cum < end_offset: one contiguous index
+// range, found in one walk of at most 14 cum values) and so its vertex count;
+// a sum-scan gives its first vertex, the carry going forward from chunk to
+// chunk.  Then the lanes turn to the chunk's output vertices, 64 at a time: a
+// lane finds its vertex's record by a 6-step search over the scanned counts,
+// makes the vertex (an end: the Coordinate; an interior point: the shape point
+// itself), quantises it, takes the vertex before it from the lane below (lane
+// 0: the carry; the trace's first: (0, 0)), and forms the two zigzag values and
+// their char counts; a second sum-scan gives its byte position.
+// WRITE false stores the trace's vertex and byte counts; WRITE true stores the
+// vertices (8 bytes a lane, consecutive), the spans from the record lanes and
+// the chars, each lane's at its own position, all at the scanned offsets and
+// never past the trace's own extent.  Every load is of the trace's own region
+// and of an edge's own shape range.
+template <bool WRITE>
+__global__ __launch_bounds__(TB) void k_shape(DevGraph g, int32_t n_traces, const int64_t* seg_base, DevTrav tv,
+                                              DevShape sh) {
+  const int lane = threadIdx.x;
+  for (int32_t t = blockIdx.x; t < n_traces; t += gridDim.x) {
+    const otm_traversal* reg = tv.rec + seg_base[t];
+    const int n = (int)tv.cnt[t];
+    int64_t vb = 0, vcap = 0, pb = 0, pcap = 0, sb = 0;
+    if (WRITE) {
+      vb = sh.vtx_off[t];
+      vcap = sh.vtx_off[t + 1] - vb;
+      pb = sh.poly_off[t];
+      pcap = sh.poly_off[t + 1] - pb;
+      sb = sh.trav_off[t];
+    }
+    // carried from chunk to chunk: the vertices and bytes so far, the last vertex
+    int64_t c_v = 0, c_b = 0;
+    int c_lat = 0, c_lon = 0;
+    for (int c0 = 0; c0 < n; c0 += TB) {
+      const int r = c0 + lane;
+      const bool in = r < n;
+      int32_t s0 = 0, m = 0, i0 = 1, nint = 0;
+      float bo = 0.0f, zo = 0.0f;
+      bool cs = false;
+      if (in) {
+        const otm_traversal* q = reg + r;
+        const int32_t e = q->edge;
+        cs = (q->flags & OTM_TV_CHAIN_START) != 0;
+        bo = q->begin_offset;
+        zo = q->end_offset;
+        s0 = g.e_shape_off[e];
+        m = g.e_shape_off[e + 1] - s0 - 1;
+        int i1 = 1;
+        for (int i = 1; i < m; ++i) {
+          const float c = g.s_cum[s0 + i];
+          if (!(bo < c)) {
+            i0 = i1 = i + 1;
+            continue;
+          }
+          if (!(c < zo)) break;
+          i1 = i + 1;
+        }
+        nint = i1 - i0;
+      }
+      const int nv = in ? (cs ? 1 : 0) + nint + 1 : 0;
+      const int incl = wave_incl_scan(nv, lane);
+      const int excl = incl - nv;
+      const int total = __shfl(incl, 63, 64);
+      if (WRITE && in) {
+        // (a record that starts no chain shares its first vertex with the record before)
+        const int32_t bv = (int32_t)(c_v + excl) - (cs ? 0 : 1), ev = (int32_t)(c_v + incl) - 1;
+        ((int2*)sh.span)[sb + r] = make_int2(bv, ev);
+      }
+      for (int v0 = 0; v0 < total; v0 += TB) {
+        const int j = v0 + lane;
+        const bool act = j < total;
+        // the owning record: the lowest one whose scanned count exceeds j
+        int own = 0;
+#pragma unroll
+        for (int step = 32; step; step >>= 1) {
+          const int val = __shfl(incl, own + step - 1, 64);
+          if (val <= j) own += step;
+        }
+        const int o_s0 = __shfl(s0, own, 64), o_m = __shfl(m, own, 64), o_i0 = __shfl(i0, own, 64);
+        const int o_nint = __shfl(nint, own, 64), o_ex = __shfl(excl, own, 64), o_cs = __shfl((int)cs, own, 64);
+        const float o_b = __shfl(bo, own, 64), o_z = __shfl(zo, own, 64);
+        int qlat = 0, qlon = 0;
+        if (act) {
+          int k = j - o_ex;
+          double la, lo;
+          if (o_cs && k == 0) {
+            shape_coord(g, o_s0, o_m, o_b, la, lo);
+          } else {
+            k -= o_cs;
+            if (k < o_nint) {
+              la = (double)g.s_lat[o_s0 + o_i0 + k];
+              lo = (double)g.s_lon[o_s0 + o_i0 + k];
+            } else {
+              shape_coord(g, o_s0, o_m, o_z, la, lo);
+            }
+          }
+          qlat = (int32_t)rint(la * 1e6);
+          qlon = (int32_t)rint(lo * 1e6);
+        }
+        int plat = __shfl_up(qlat, 1, 64), plon = __shfl_up(qlon, 1, 64);
+        if (lane == 0) {
+          plat = c_lat;
+          plon = c_lon;
+        }
+        const int dla = qlat - plat, dlo = qlon - plon;
+        const uint32_t za = ((uint32_t)dla << 1) ^ (uint32_t)(dla >> 31);
+        const uint32_t zb = ((uint32_t)dlo << 1) ^ (uint32_t)(dlo >> 31);
+        const int na = 1 + (31 - __clz((int)(za | 1u))) / 5, nb = 1 + (31 - __clz((int)(zb | 1u))) / 5;
+        const int nby = act ? na + nb : 0;
+        const int binc = wave_incl_scan(nby, lane);
+        if (WRITE && act) {
+          const int64_t vi = c_v + j, bp = c_b + binc - nby;
+          if (vi < vcap) ((int2*)sh.vtx)[vb + vi] = make_int2(qlat, qlon);
+          if (bp + nby <= pcap) shape_put(shape_put(sh.poly + pb + bp, za, na), zb, nb);
+        }
+        const int last = (total - v0 < TB ? total - v0 : TB) - 1;
+        c_lat = __shfl(qlat, last, 64);
+        c_lon = __shfl(qlon, last, 64);
+        c_b += __shfl(binc, 63, 64);
+      }
+      c_v += total;
+    }
+    if (!WRITE && lane == 0) {
+      sh.vtx_off[t] = c_v;
+      sh.poly_off[t] = c_b;
+    }
+  }
+}
+
 int grid_for(int64_t n, int per_block, int cap) {
   int64_t g = (n + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -5893,6 +6055,14 @@ void launch_trav_compact(int32_t n_traces, const int64_t* seg_base, const int64_
                          otm_traversal* dst, hipStream_t s) {
   hipLaunchKernelGGL(k_trav_compact, dim3(grid_for(n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, n_traces, seg_base, off,
                      reg, dst);
+}
+void launch_shape(const DevGraph& g, int32_t n_traces, const int64_t* seg_base, const DevTrav& tv, const DevShape& sh,
+                  bool write, hipStream_t s) {
+  const dim3 grid(grid_for(n_traces, 1, WAVE_GRID_CAP));
+  if (write)
+    hipLaunchKernelGGL(k_shape<true>, grid, dim3(TB), 0, s, g, n_traces, seg_base, tv, sh);
+  else
+    hipLaunchKernelGGL(k_shape<false>, grid, dim3(TB), 0, s, g, n_traces, seg_base, tv, sh);
 }
 void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* tb, hipStream_t s,
                       const Marks& mk) {

@@ -125,7 +125,7 @@ class Results(object):
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
                  trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, matched_points=False,
-                 traversals=False, scores=False, **meili):
+                 traversals=False, scores=False, shape=False, **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
         with ndev > 1): traces go to member murmur2(uuid) % ndev.
@@ -134,6 +134,8 @@ class Engine(object):
         traversals: the per-edge records of rule 7d (set_traversals /
         traversals; off: nothing changes).
         scores: the per-point match scores of rule 7e (set_scores / scores;
+        off: nothing changes).
+        shape: the matched route's geometry of rule 7f (set_shape / shape;
         off: nothing changes)."""
         L = lib()
         self._tmp = None
@@ -160,6 +162,8 @@ class Engine(object):
             self.set_traversals(True)
         if scores:
             self.set_scores(True)
+        if shape:
+            self.set_shape(True)
 
     def members(self):
         """Member count: ndev of a multi-device engine, else 1."""
@@ -444,7 +448,7 @@ class Engine(object):
         return k.value
 
     # The optional per-batch outputs (matched points, matched route, match
-    # scores): one switch, one info call, one fetch and one device call each,
+    # scores, matched shape): one switch, one info call, one fetch and one device call each,
     # the same but for the C function's name and the record's dtype.
     def _set_switch(self, fn, on):
         _check(getattr(lib(), fn)(self.h, 1 if on else 0))
@@ -532,6 +536,43 @@ class Engine(object):
         """(device pointer, count) of the last batch's records in this GPU's HBM
         (otm_scores_device; a one-device engine's, valid until its next batch)."""
         return self._records_device("otm_scores_device")
+
+    def set_shape(self, on):
+        """The matched-shape switch of this handle (otm_set_shape; a multi-device
+        engine passes it to every member, a clone inherits it when it is made)."""
+        self._set_switch("otm_set_shape", on)
+
+    def shape_info(self):
+        """Whether the matched shape is on (otm_shape_info)."""
+        return self._switch_info("otm_shape_info")
+
+    def shape(self):
+        """The matched shape of the handle's last binary-level batch
+        (otm_shape_size, otm_fetch_shape): (vertices, vtx_off, spans, trav_off,
+        polyline_bytes, poly_off) -- _lib.SHAPE_VERTEX_DTYPE vertices in
+        microdegrees, trace t's at [vtx_off[t], vtx_off[t + 1]); one
+        _lib.SHAPE_SPAN_DTYPE span of trace-relative vertex indices per
+        traversal, in traversals()' order and offsets; the traces' polyline6
+        strings in one bytes object, trace t's at [poly_off[t], poly_off[t + 1])."""
+        z = _lib.ShapeSizes()
+        _check(lib().otm_shape_size(self.h, C.byref(z)))
+        vtx = np.zeros(z.n_vertices, dtype=_lib.SHAPE_VERTEX_DTYPE)
+        spans = np.zeros(z.n_traversals, dtype=_lib.SHAPE_SPAN_DTYPE)
+        poly = np.zeros(z.n_bytes, dtype=np.uint8)
+        offs = [np.zeros(z.n_traces + 1, dtype=np.int64) for _ in range(3)]
+        dst = _lib.ShapeOut(vtx.ctypes.data if len(vtx) else None, len(vtx), offs[0].ctypes.data,
+                            spans.ctypes.data if len(spans) else None, len(spans), offs[1].ctypes.data,
+                            poly.ctypes.data if len(poly) else None, len(poly), offs[2].ctypes.data)
+        _check(lib().otm_fetch_shape(self.h, C.byref(dst)))
+        return vtx, offs[0], spans, offs[1], poly.tobytes(), offs[2]
+
+    def shape_device(self):
+        """The last batch's matched shape in this GPU's HBM (otm_shape_device; a
+        one-device engine's, valid until its next batch): (_lib.ShapeOut of
+        device pointers, its caps the counts; _lib.ShapeSizes)."""
+        dev, z = _lib.ShapeOut(), _lib.ShapeSizes()
+        _check(lib().otm_shape_device(self.h, C.byref(dev), C.byref(z)))
+        return dev, z
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))
