@@ -588,6 +588,81 @@ int otm_shape_size(otm_engine* eng, otm_shape_sizes* out);
 int otm_fetch_shape(otm_engine* eng, const otm_shape_out* dst);
 int otm_shape_device(otm_engine* eng, otm_shape_out* dev, otm_shape_sizes* n);
 
+/* Trace attributes (extension, DESIGN.md §3 rule 7g): the four outputs above as
+ * text -- one JSON body per trace of the last binary-level batch, made on the
+ * GPU (attributes.hip) from the batch's records as they stand, delivered as one
+ * dense char blob with per-trace offsets, so a caller needs no struct layout.
+ * The rule decides nothing new: a body is a pure function of the trace's
+ * otm_matched_point, otm_point_score and otm_traversal records, its
+ * otm_shape_span records and polyline, and the section mask.  Off by default
+ * (mask 0), per handle: with it off nothing is launched or allocated; with it
+ * on, a binary-level match also runs k_points (OTM_ATTR_POINTS), k_scores
+ * (OTM_ATTR_SCORES) and k_traversals (OTM_ATTR_EDGES or OTM_ATTR_SHAPE), whether
+ * or not their own switches are on (those keep their own answers), and
+ * everything else happens at the first size, fetch or device call for the
+ * batch.  A clone inherits its parent's mask when it is made; a multi-device
+ * engine passes the call to every member.
+ *   Body, without whitespace, keys in this order, a section whose bit is off
+ *   absent with its comma:
+ *     {"matched_points":[MP,...],"edges":[E,...],"shape":"S"}
+ *   MP, one per input point in input order: with OTM_PT_MATCHED
+ *     {"type":T,"edge_id":i,"way_id":i,"lat":F6,"lon":F6,"distance_along_edge":F3,
+ *      "distance_from_trace_point":F3,"flags":i}
+ *   T "matched" with OTM_PT_COLUMN, else "interpolated"; without OTM_PT_MATCHED
+ *     {"type":"unmatched","flags":i}
+ *   and, with OTM_ATTR_SCORES and OTM_SC_SCORED in the point's score record,
+ *   before the closing brace
+ *     ,"score":{"cost":F6,"margin":F6,"chain_cost":F6,"emission":F6,"transition":F6,
+ *      "ncand":i,"state":i,"alt":i,"alt_edge":i,"alt_offset":F3,"flags":i}
+ *   E, one per traversal in otm_fetch_traversals' order:
+ *     {"id":i,"way_id":i,"begin_offset":F3,"end_offset":F3,"enter_time":F3,"exit_time":F3,
+ *      "begin_shape_index":i,"end_shape_index":i,"segment":i,"flags":i}
+ *   with OTM_ATTR_SHAPE also ,"begin_vertex":i,"end_vertex":i before ,"flags".
+ *   S: the trace's polyline6 string, each backslash (byte 92) doubled.
+ *   i: a decimal integer.  F3(x), F6(x): x widened to double; v = x * 1000.0 (or
+ *   x * 1e6), one double product; !(fabs(v) < 2^53) gives null (NaN, the
+ *   infinities: the margin of OTM_SC_ALONE); else n = (int64)rint(v), round half
+ *   even; the text is '-' when n < 0, |n| / 10^d, '.', |n| % 10^d in d digits
+ *   (-0.0004 -> 0.000, -0.0015 -> -0.002, 12 -> 12.000).
+ * Validity: only the three binary-level calls leave attributes; any later
+ * batch on the handle, any JSON-level call on it and any failed batch end them:
+ * a call then answers OTM_EINVAL, never another batch's bodies. */
+#define OTM_ATTR_POINTS 1u /* "matched_points" */
+#define OTM_ATTR_SCORES 2u /* ... with "score" objects; needs OTM_ATTR_POINTS */
+#define OTM_ATTR_EDGES 4u  /* "edges" */
+#define OTM_ATTR_SHAPE 8u  /* "shape", and the edges' vertex spans */
+#define OTM_ATTR_ALL 15u
+/* otm_set_attributes: the section mask (0: off) that the handle's next batches
+ * run with.  A batch's bodies are made from the mask the batch ran with: a mask
+ * set between a batch and its first size, fetch or device call changes nothing
+ * of that batch's bodies (mask 0 there answers OTM_EINVAL, "off", as the other
+ * switches do).  A bad mask is OTM_EINVAL on any handle, NULL too.
+ * otm_attributes_info: the handle's mask (mask not NULL).
+ * otm_attributes_size: the trace count and the blob's bytes of the batch the
+ * fetch answers for (neither pointer NULL).  otm_fetch_attributes answers for the handle's
+ * last otm_match_soa, otm_match_compact or otm_match_device batch, any number of
+ * times with the same bytes: trace t's body at [body_off[t], body_off[t + 1])
+ * of dst[cap] (body_off[n_traces + 1], may be NULL), no terminator and nothing
+ * between bodies; cap 0 with dst NULL only sizes the call.  On a multi-device
+ * engine the members' bodies are joined in the batch's trace order (only
+ * body_off is rebased).  otm_attributes_device: the device arrays of a
+ * one-device engine (valid until its next batch), ordered behind the engine's
+ * stream.  otm_debug_attr_fixed: F3 (decimals 3) or F6 (6) of x into out (at
+ * least 24 bytes, NUL-terminated), the length returned; the host face of the
+ * formatter the GPU runs.  OTM_EINVAL (message in otm_last_error): a NULL
+ * engine or argument, a mask with a bit above OTM_ATTR_ALL or with
+ * OTM_ATTR_SCORES without OTM_ATTR_POINTS (the mask then stays as it was), a
+ * size, fetch or device call with the mask 0 or with no binary-level batch with
+ * it on as the handle's last batch, cap below the byte count,
+ * otm_attributes_device on a multi-device handle, decimals other than 3 or 6. */
+int otm_set_attributes(otm_engine* eng, uint32_t mask);
+int otm_attributes_info(const otm_engine* eng, uint32_t* mask);
+int otm_attributes_size(otm_engine* eng, int64_t* n_traces, int64_t* n_bytes);
+int otm_fetch_attributes(otm_engine* eng, char* dst, int64_t cap, int64_t* body_off, int64_t* n_bytes);
+int otm_attributes_device(otm_engine* eng, const char** dev, const int64_t** body_off, int64_t* n_traces,
+                          int64_t* n_bytes);
+int otm_debug_attr_fixed(double x, int decimals, char* out);
+
 /* Per-segment speed histogram, accumulated on the device by every match
  * call: counts u32[n_segments * nbins], bin = floor(kph / bin_kph) clamped to
  * nbins-1, one count per datastore report.  The buffer is CALLER-owned device

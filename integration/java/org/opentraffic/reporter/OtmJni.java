@@ -39,6 +39,12 @@ public final class OtmJni {
 
   public static native void windowEnd();
 
+  /** The trace attributes' section mask (OTM_ATTR_*; 0: off), and the last matchCompact batch's bodies:
+   * [0] the blob (byte[]), [1] bodyOff (long[nTraces + 1]).  A failure throws IllegalStateException. */
+  public static native void setAttributes(int mask);
+
+  public static native Object[] attributes();
+
   /**
    * Pair windows (otm_pairs_begin / _flush / _end): the reports aggregated per (time bucket, segment, next
    * segment).  pairsFlush, called between batches, returns the window's body and the window goes on empty.

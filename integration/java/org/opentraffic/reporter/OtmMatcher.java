@@ -115,6 +115,17 @@ public final class OtmMatcher {
   // int otm_match_compact(otm_engine*, const otm_batch_compact* in, otm_results* out)
   private static final MethodHandle MATCH_COMPACT = fn("otm_match_compact",
       FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS, ValueLayout.ADDRESS));
+  // Trace attributes (include/otmatch.h, "Trace attributes"): plain integer out-parameters, no struct layout
+  // int otm_set_attributes(otm_engine*, uint32_t mask)
+  private static final MethodHandle SET_ATTRIBUTES = fn("otm_set_attributes",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.JAVA_INT));
+  // int otm_attributes_size(otm_engine*, int64_t* n_traces, int64_t* n_bytes)
+  private static final MethodHandle ATTRIBUTES_SIZE = fn("otm_attributes_size",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS, ValueLayout.ADDRESS));
+  // int otm_fetch_attributes(otm_engine*, char* dst, int64_t cap, int64_t* body_off, int64_t* n_bytes)
+  private static final MethodHandle FETCH_ATTRIBUTES = fn("otm_fetch_attributes",
+      FunctionDescriptor.of(ValueLayout.JAVA_INT, ValueLayout.ADDRESS, ValueLayout.ADDRESS, ValueLayout.JAVA_LONG,
+          ValueLayout.ADDRESS, ValueLayout.ADDRESS));
   // void* otm_host_alloc(size_t); void otm_host_free(void*): page-locked buffers the library DMAs from
   private static final MethodHandle HOST_ALLOC = fn("otm_host_alloc",
       FunctionDescriptor.of(ValueLayout.ADDRESS, ValueLayout.JAVA_LONG));
@@ -236,6 +247,39 @@ public final class OtmMatcher {
       MemorySegment kph = a.allocate(ValueLayout.JAVA_FLOAT);
       check((int) QUEUE_INFO.invokeExact(ENGINE, kph), "otm_queue_info");
       return kph.get(ValueLayout.JAVA_FLOAT, 0);
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /** The trace attributes' section mask (OTM_ATTR_*: 1 points, 2 scores, 4 edges, 8 shape; 0: off). */
+  public static void setAttributes(int mask) {
+    try {
+      check((int) SET_ATTRIBUTES.invokeExact(ENGINE, mask), "otm_set_attributes");
+    } catch (Throwable t) {
+      throw new IllegalStateException(t);
+    }
+  }
+
+  /** The last matchCompact batch's JSON bodies: trace t's is blob[bodyOff[t], bodyOff[t + 1]) (ASCII). */
+  public record Attributes(byte[] blob, long[] bodyOff) {
+    public String body(int t) {
+      return new String(blob, (int) bodyOff[t], (int) (bodyOff[t + 1] - bodyOff[t]), StandardCharsets.US_ASCII);
+    }
+  }
+
+  /** One JSON document per trace of the last matchCompact batch (setAttributes first), written on the GPU. */
+  public static Attributes attributes() {
+    try (Arena a = Arena.ofConfined()) {
+      MemorySegment nt = a.allocate(ValueLayout.JAVA_LONG);
+      MemorySegment nb = a.allocate(ValueLayout.JAVA_LONG);
+      check((int) ATTRIBUTES_SIZE.invokeExact(ENGINE, nt, nb), "otm_attributes_size");
+      long traces = nt.get(ValueLayout.JAVA_LONG, 0), bytes = nb.get(ValueLayout.JAVA_LONG, 0);
+      MemorySegment dst = a.allocate(Math.max(bytes, 1));
+      MemorySegment off = a.allocate(ValueLayout.JAVA_LONG, traces + 1);
+      check((int) FETCH_ATTRIBUTES.invokeExact(ENGINE, bytes == 0 ? MemorySegment.NULL : dst, bytes, off, nb),
+          "otm_fetch_attributes");
+      return new Attributes(dst.asSlice(0, bytes).toArray(ValueLayout.JAVA_BYTE), off.toArray(ValueLayout.JAVA_LONG));
     } catch (Throwable t) {
       throw new IllegalStateException(t);
     }

@@ -81,6 +81,38 @@ JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_windowEnd(JNIEnv* en
   if (otm_window_end(g_eng) != OTM_OK) throw_last(env);
 }
 
+/* OtmJni.setAttributes / attributes: trace attributes (include/otmatch.h, "Trace attributes") -- the blob as
+ * a byte[] and body_off as a long[], in an Object[2]. */
+JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_setAttributes(JNIEnv* env, jclass c, jint mask) {
+  (void)c;
+  if (otm_set_attributes(g_eng, (uint32_t)mask) != OTM_OK) throw_last(env);
+}
+
+JNIEXPORT jobjectArray JNICALL Java_org_opentraffic_reporter_OtmJni_attributes(JNIEnv* env, jclass c) {
+  (void)c;
+  int64_t nt = 0, nb = 0;
+  if (otm_attributes_size(g_eng, &nt, &nb) != OTM_OK) {
+    throw_last(env);
+    return NULL;
+  }
+  jbyteArray blob = (*env)->NewByteArray(env, (jsize)nb);
+  jlongArray off = (*env)->NewLongArray(env, (jsize)(nt + 1));
+  jobjectArray out = (*env)->NewObjectArray(env, 2, (*env)->FindClass(env, "java/lang/Object"), NULL);
+  if (!blob || !off || !out) return NULL;
+  jbyte* b = nb ? (*env)->GetByteArrayElements(env, blob, NULL) : NULL;
+  jlong* o = (*env)->GetLongArrayElements(env, off, NULL);
+  const int rc = (nb && !b) || !o ? OTM_EINVAL : otm_fetch_attributes(g_eng, (char*)b, nb, (int64_t*)o, &nb);
+  if (b) (*env)->ReleaseByteArrayElements(env, blob, b, 0);
+  if (o) (*env)->ReleaseLongArrayElements(env, off, o, 0);
+  if (rc != OTM_OK) {
+    throw_last(env);
+    return NULL;
+  }
+  (*env)->SetObjectArrayElement(env, out, 0, blob);
+  (*env)->SetObjectArrayElement(env, out, 1, off);
+  return out;
+}
+
 /* OtmJni.pairsBegin / pairsFlush / pairsEnd: the pair window (include/otmatch.h, "Pair windows"), as the
  * histogram window above. */
 JNIEXPORT void JNICALL Java_org_opentraffic_reporter_OtmJni_pairsBegin(JNIEnv* env, jclass c, jint bucket_s,

@@ -187,6 +187,9 @@ class ShapeOut(C.Structure):
                 ("polyline", C.c_void_p), ("polyline_cap", C.c_int64), ("poly_off", C.c_void_p)]
 
 
+# the section mask of trace attributes (OTM_ATTR_*, include/otmatch.h)
+ATTR_POINTS, ATTR_SCORES, ATTR_EDGES, ATTR_SHAPE, ATTR_ALL = 1, 2, 4, 8, 15
+
 SEG_START_VALID, SEG_END_VALID, SEG_INTERNAL, SEG_START_INT, SEG_END_INT = 1, 2, 4, 8, 16
 REP_T1_INT, REP_T0_INT = 1, 2
 REP_T1_INT_MINUS1 = REP_T1_INT
@@ -222,6 +225,12 @@ def _declare(L):
         "otm_shape_size": (C.c_int, [vp, C.POINTER(ShapeSizes)]),
         "otm_fetch_shape": (C.c_int, [vp, C.POINTER(ShapeOut)]),
         "otm_shape_device": (C.c_int, [vp, C.POINTER(ShapeOut), C.POINTER(ShapeSizes)]),
+        "otm_set_attributes": (C.c_int, [vp, C.c_uint32]),
+        "otm_attributes_info": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "otm_attributes_size": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+        "otm_fetch_attributes": (C.c_int, [vp, vp, i64, vp, C.POINTER(i64)]),
+        "otm_attributes_device": (C.c_int, [vp, pp, pp, C.POINTER(i64), C.POINTER(i64)]),
+        "otm_debug_attr_fixed": (C.c_int, [C.c_double, C.c_int, C.c_char_p]),
         "otm_request_points": (C.c_int, [C.c_char_p, sz, C.c_int, vp, vp, vp, vp, C.c_int, C.c_char_p, sz]),
         "otm_engine_member": (vp, [vp, C.c_int]),
         "otm_engine_destroy": (None, [vp]),

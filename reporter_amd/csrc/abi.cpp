@@ -19,6 +19,7 @@
 #include <sstream>
 #include <thread>
 
+#include "attrfmt.h"
 #include "engine.h"
 #include "flush.h"
 #include "javastr.h"
@@ -1989,18 +1990,27 @@ struct BinaryBatch {
   ~BinaryBatch() { E->binary_batch = false; }
 };
 
+// a binary-level call that its arguments fail ends what REC_CALL_FAILED ends, as one that fails later does
+static int bad_binary_call(otm_engine* E, const char* msg) {
+  otm::end_records(E, otm::REC_CALL_FAILED);
+  return fail(OTM_EINVAL, msg);
+}
+
 static int otm_match_soa_impl(otm_engine* E, const otm_batch* in, otm_results* out) {
-  if (!E || !in || !out) return fail(OTM_EINVAL, "bad arguments");
+  if (!E) return fail(OTM_EINVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(E->mu);
+  if (!in || !out) return bad_binary_call(E, "bad arguments");
   BinaryBatch bb(E);
   std::string err;
   int rc = otm::match_host_fetch(E, in, nullptr, out, &err);
+  if (rc) otm::end_records(E, otm::REC_CALL_FAILED);
   return rc ? fail(rc, err) : OTM_OK;
 }
 
 static int otm_match_compact_impl(otm_engine* E, const otm_batch_compact* in, otm_results* out) {
-  if (!E || !in || !out) return fail(OTM_EINVAL, "bad arguments");
+  if (!E) return fail(OTM_EINVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(E->mu);
+  if (!in || !out) return bad_binary_call(E, "bad arguments");
   BinaryBatch bb(E);
   std::string err;
   int rc;
@@ -2013,7 +2023,10 @@ static int otm_match_compact_impl(otm_engine* E, const otm_batch_compact* in, ot
     // after the same checks as one engine's
     const int32_t nt = in->n_traces;
     int64_t np = 0;
-    if ((rc = otm::validate_compact(in, &np, &err))) return fail(rc, err);
+    if ((rc = otm::validate_compact(in, &np, &err))) {
+      otm::end_records(E, otm::REC_CALL_FAILED);
+      return fail(rc, err);
+    }
     std::vector<double> tm((size_t)np);
     std::vector<float> acc((size_t)np);
     for (int32_t t = 0; t < nt; ++t)
@@ -2023,13 +2036,15 @@ static int otm_match_compact_impl(otm_engine* E, const otm_batch_compact* in, ot
     const otm_batch b{nt, np, in->trace_off, in->lat, in->lon, tm.data(), acc.data()};
     rc = otm::match_host_fetch(E, &b, nullptr, out, &err);
   }
+  if (rc) otm::end_records(E, otm::REC_CALL_FAILED);
   return rc ? fail(rc, err) : OTM_OK;
 }
 
 static int otm_match_device_impl(otm_engine* E, const otm_batch* in, void* stream) {
-  if (!E || !in) return fail(OTM_EINVAL, "bad arguments");
-  if (!E->members.empty()) return fail(OTM_EINVAL, "device batches go to a member engine (otm_engine_member)");
+  if (!E) return fail(OTM_EINVAL, "bad arguments");
   std::lock_guard<std::mutex> lk(E->mu);
+  if (!in) return bad_binary_call(E, "bad arguments");
+  if (!E->members.empty()) return bad_binary_call(E, "device batches go to a member engine (otm_engine_member)");
   BinaryBatch bb(E);
   (void)hipSetDevice(E->device);
   otm::DevBatch b;
@@ -2044,6 +2059,7 @@ static int otm_match_device_impl(otm_engine* E, const otm_batch* in, void* strea
   E->spin_waits = true;  // (wait_batch: the caller's threads drive the GPU)
   int rc = otm::engine_match(E, b, (hipStream_t)stream, &err);
   E->spin_waits = false;
+  if (rc) otm::end_records(E, otm::REC_CALL_FAILED);
   return rc ? fail(rc, err) : OTM_OK;
 }
 
@@ -2495,6 +2511,89 @@ int otm_shape_device(otm_engine* E, otm_shape_out* dev, otm_shape_sizes* n) {
     if (n) *n = z;
     return (int)OTM_OK;
   });
+}
+
+// Trace attributes (rule 7g): a section mask where the other outputs have a switch, one char blob with
+// per-trace offsets; the first size, fetch or device call of a batch makes it (engine_attributes_make).
+// (The mask is checked before the handle: a bad mask is OTM_EINVAL on any handle.)  The mask is the next
+// batch's: the last batch's bodies are made from the mask it ran with (otm_engine::at_batch_mask).
+int otm_set_attributes(otm_engine* E, uint32_t mask) {
+  if (mask & ~OTM_ATTR_ALL) return fail(OTM_EINVAL, "trace attributes: the mask has a bit above OTM_ATTR_ALL");
+  if ((mask & OTM_ATTR_SCORES) && !(mask & OTM_ATTR_POINTS))
+    return fail(OTM_EINVAL, "trace attributes: OTM_ATTR_SCORES needs OTM_ATTR_POINTS");
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  std::lock_guard<std::mutex> lk(E->mu);
+  for (otm_engine* mem : E->members) {
+    std::lock_guard<std::mutex> ml(mem->mu);
+    mem->at_mask = mask;
+    mem->attrs.on = mask != 0;
+  }
+  E->at_mask = mask;
+  E->attrs.on = mask != 0;
+  return OTM_OK;
+}
+
+int otm_attributes_info(const otm_engine* E, uint32_t* mask) {
+  if (!E || !mask) return fail(OTM_EINVAL, otm::kRecDesc<char>.dev_null);
+  std::lock_guard<std::mutex> lk(const_cast<otm_engine*>(E)->mu);
+  *mask = E->at_mask;
+  return OTM_OK;
+}
+
+int otm_attributes_size(otm_engine* E, int64_t* n_traces, int64_t* n_bytes) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<char>;
+  if (!E || !n_traces || !n_bytes) return fail(OTM_EINVAL, d.dev_null);
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (!E->members.empty()) {
+      if (!E->attrs.on) return fail(OTM_EINVAL, d.off);
+      if (E->attrs.joined_n < 0) return fail(OTM_EINVAL, d.none);
+      if (n_traces) *n_traces = (int64_t)E->g_at_off.size() - 1;
+      if (n_bytes) *n_bytes = E->attrs.joined_n;
+      return (int)OTM_OK;
+    }
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    std::string err;
+    const int rc = otm::engine_attributes_make(E, n_traces, n_bytes, &err);
+    return rc ? fail(rc, err) : (int)OTM_OK;
+  });
+}
+
+int otm_fetch_attributes(otm_engine* E, char* dst, int64_t cap, int64_t* body_off, int64_t* n_bytes) {
+  return records_fetch(
+      E, &otm_engine::attrs, dst, cap, n_bytes,
+      [&](std::string* err) { return otm::engine_fetch_attributes(E, dst, cap, body_off, n_bytes, err); },
+      [&] {
+        if (body_off) std::memcpy(body_off, E->g_at_off.data(), E->g_at_off.size() * sizeof(int64_t));
+      });
+}
+
+int otm_attributes_device(otm_engine* E, const char** dev, const int64_t** body_off, int64_t* n_traces,
+                          int64_t* n_bytes) {
+  constexpr const otm::RecDesc& d = otm::kRecDesc<char>;
+  if (!E || !dev) return fail(OTM_EINVAL, d.dev_null);
+  if (!E->members.empty()) return fail(OTM_EINVAL, "a device buffer belongs to a member engine (otm_engine_member)");
+  return guarded([&] {
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (E->device >= 0) (void)hipSetDevice(E->device);
+    int64_t nt = 0, nb = 0;
+    std::string err;
+    if (const int rc = otm::engine_attributes_make(E, &nt, &nb, &err)) return fail(rc, err);
+    *dev = nb ? E->attrs.dev.p : nullptr;
+    if (body_off) *body_off = E->at_off.p;
+    if (n_traces) *n_traces = nt;
+    if (n_bytes) *n_bytes = nb;
+    return (int)OTM_OK;
+  });
+}
+
+int otm_debug_attr_fixed(double x, int decimals, char* out) {
+  if (!out || (decimals != 3 && decimals != 6)) return fail(OTM_EINVAL, "out is NULL or decimals is neither 3 nor 6");
+  otm::pyrepr::CharSink s{out, 0};
+  if (decimals == 3) otm::attrfmt::fixed<3>(x, s);
+  else otm::attrfmt::fixed<6>(x, s);
+  out[s.n] = '\0';
+  return s.n;
 }
 
 int otm_index_tables(const otm_engine* E, int64_t* slots, int64_t* bytes, int32_t* load_pct) {

@@ -390,6 +390,8 @@ int engine_clone(const otm_engine* P, otm_engine* C, std::string* err, bool own_
   C->route.on = P->route.on;
   C->scores.on = P->scores.on;
   C->shape.on = P->shape.on;
+  C->attrs.on = P->attrs.on;
+  C->at_mask = P->at_mask;
   C->mc = P->mc;
   C->rc = P->rc;
   C->dp = P->dp;
@@ -901,33 +903,41 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   if (E->queue_kph > 0.0f) launch_queue(b, w, o, E->queue_kph, s);
   // K7c (DESIGN.md §3 rule 7c): only with the handle's switch on; outside the timing marks.
   // Every attempt writes the whole array, so a redone or resumed batch leaves one run's records.
+  // Trace attributes (rule 7g) are made from K7c's, K7e's and K7d's records at their first fetch: the
+  // mask's bits run those kernels too, and leave the outputs' own switches and counts alone.
+  const uint32_t attr = records_wanted(E, E->attrs) ? E->at_mask : 0;
   end_records(E, REC_BATCH_OUTPUTS);
-  if (records_wanted(E, E->points)) {
+  if (records_wanted(E, E->points) || (attr & OTM_ATTR_POINTS)) {
     TRY(E->points.dev.ensure((size_t)NP + 1, err));
     launch_points(E->g, b, dp, w, E->points.dev.p, s);
-    E->points.n = NP;
+    if (records_wanted(E, E->points)) E->points.n = NP;
   }
   // K7e (DESIGN.md §3 rule 7e): beside K7c, only with the handle's switch on and only for a binary-level
   // batch; outside the timing marks.  It reads what K3-K5 left, which nothing after K5 writes before the
   // next batch, and trace_err as route recovery left it (launched after launch_route: K6 can still fail a
   // trace, whose records are then all zero); every attempt writes the whole array.
-  if (records_wanted(E, E->scores)) {
+  if (records_wanted(E, E->scores) || (attr & OTM_ATTR_SCORES)) {
     DevScores sc{};
     TRY(bind_scores(E, NT, NP, sc, err));
     launch_scores(b, w, sc, s);
-    E->scores.n = NP;
+    if (records_wanted(E, E->scores)) E->scores.n = NP;
   }
   // K7d (DESIGN.md §3 rule 7d): likewise, and only for a binary-level batch.  Every attempt writes
   // each trace's whole count and region; the dense form is made at the first fetch.
   // The matched shape (rule 7f) is made from these records at its first fetch: its switch runs K7d too.
   const bool for_route = records_wanted(E, E->route), for_shape = records_wanted(E, E->shape);
-  if (for_route || for_shape) {
+  if (for_route || for_shape || (attr & (OTM_ATTR_EDGES | OTM_ATTR_SHAPE))) {
     DevTrav tv{};
     TRY(bind_trav(E, NT, NP, tv, err));
     HIPCHK(hipMemsetAsync(tv.cnt + NT, 0, sizeof *tv.cnt, s));
     launch_traversals(E->g, b, w, o, tv, s);
     if (for_route) E->tv_T = NT;
     if (for_shape) E->sh_T = NT;
+  }
+  if (attr) {
+    E->at_T = NT;
+    E->at_P = NP;
+    E->at_batch_mask = attr;
   }
   launch_report(b, E->drc, w, o, s, mk);
   HIPCHK(hipGetLastError());
@@ -1687,6 +1697,8 @@ void end_records(otm_engine* E, RecEvent event) {
   // (the regions the route's dense form and the shape are made from, and their scanned counts)
   if (kRecDesc<otm_traversal>.ends & event) E->tv_T = E->tv_off_T = -1;
   if (kRecDesc<otm_shape_vertex>.ends & event) E->sh_T = -1;
+  end_if(E->attrs, event);
+  if (kRecDesc<char>.ends & event) E->at_T = -1;
 }
 
 template <class Rec>
@@ -1739,18 +1751,11 @@ static int trav_offsets(otm_engine* E, int32_t NT, std::string* err, bool wait =
   return OTM_OK;
 }
 
-int engine_traversals_dense(otm_engine* E, std::string* err) {
-  if (!E->route.on) {
-    *err = kRecDesc<otm_traversal>.off;
-    return OTM_EINVAL;
-  }
-  if (E->tv_T < 0) {
-    *err = kRecDesc<otm_traversal>.none;
-    return OTM_EINVAL;
-  }
+// The dense form of the last batch that ran k_traversals (NT its trace count), made once per batch by
+// the matched route's or the trace attributes' first call, whichever comes first (E->route.n: made).
+static int trav_dense(otm_engine* E, int32_t NT, std::string* err) {
   if (E->route.n >= 0) return OTM_OK;  // made by an earlier call for this batch
   hipStream_t s = E->stream;
-  const int32_t NT = E->tv_T;
   // dense offsets: the exclusive scan of the per-trace counts, then one copy
   // pass out of the per-trace regions
   TRY(trav_offsets(E, NT, err));
@@ -1764,6 +1769,18 @@ int engine_traversals_dense(otm_engine* E, std::string* err) {
   return OTM_OK;
 }
 
+int engine_traversals_dense(otm_engine* E, std::string* err) {
+  if (!E->route.on) {
+    *err = kRecDesc<otm_traversal>.off;
+    return OTM_EINVAL;
+  }
+  if (E->tv_T < 0) {
+    *err = kRecDesc<otm_traversal>.none;
+    return OTM_EINVAL;
+  }
+  return trav_dense(E, E->tv_T, err);
+}
+
 int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int64_t* trav_off, int64_t* n,
                             std::string* err) {
   TRY(engine_traversals_dense(E, err));
@@ -1771,17 +1788,9 @@ int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int6
   return engine_fetch_records(E, E->route, dst, cap, n, err);
 }
 
-int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err) {
-  constexpr const RecDesc& d = kRecDesc<otm_shape_vertex>;
-  if (!E->shape.on) {
-    *err = d.off;
-    return OTM_EINVAL;
-  }
-  if (E->sh_T < 0) {
-    *err = d.none;
-    return OTM_EINVAL;
-  }
-  const int32_t NT = E->sh_T;
+// The matched shape of the last batch that ran k_traversals (NT its trace count), made once per batch
+// by the shape's or the trace attributes' first call, whichever comes first (E->shape.n: made).
+static int shape_make(otm_engine* E, int32_t NT, otm_shape_sizes* sz, std::string* err) {
   const size_t T1 = (size_t)NT + 1;
   if (E->shape.n < 0) {  // (else: made by an earlier call for this batch)
     hipStream_t s = E->stream;
@@ -1823,6 +1832,19 @@ int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err) {
   return OTM_OK;
 }
 
+int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err) {
+  constexpr const RecDesc& d = kRecDesc<otm_shape_vertex>;
+  if (!E->shape.on) {
+    *err = d.off;
+    return OTM_EINVAL;
+  }
+  if (E->sh_T < 0) {
+    *err = d.none;
+    return OTM_EINVAL;
+  }
+  return shape_make(E, E->sh_T, sz, err);
+}
+
 int engine_fetch_shape(otm_engine* E, const otm_shape_out* dst, std::string* err) {
   otm_shape_sizes z;
   TRY(engine_shape_make(E, &z, err));
@@ -1857,6 +1879,81 @@ int engine_fetch_shape(otm_engine* E, const otm_shape_out* dst, std::string* err
   if (sb) std::memcpy(dst->spans, E->h_sh_span.p, sb);
   if (pb) std::memcpy(dst->polyline, E->h_sh_poly.p, pb);
   return OTM_OK;
+}
+
+int engine_attributes_make(otm_engine* E, int64_t* nt, int64_t* nb, std::string* err) {
+  constexpr const RecDesc& d = kRecDesc<char>;
+  if (!E->attrs.on) {
+    *err = d.off;
+    return OTM_EINVAL;
+  }
+  if (E->at_T < 0) {
+    *err = d.none;
+    return OTM_EINVAL;
+  }
+  const int32_t NT = E->at_T;
+  const size_t T1 = (size_t)NT + 1;
+  if (E->attrs.n < 0) {  // (else: made by an earlier call for this batch)
+    hipStream_t s = E->stream;
+    const uint32_t mask = E->at_batch_mask;  // (the batch's, not the handle's: only its bits' kernels ran)
+    // what the sections are made from, for the bits that need it (each waits for the stream)
+    if (mask & OTM_ATTR_EDGES) TRY(trav_dense(E, NT, err));
+    if (mask & OTM_ATTR_SHAPE) TRY(shape_make(E, NT, nullptr, err));
+    DevAttr a{};
+    a.mask = mask;
+    a.n_traces = NT;
+    a.n_points = (mask & OTM_ATTR_POINTS) ? E->at_P : 0;
+    a.n_trav = (mask & OTM_ATTR_EDGES) ? E->h_tv_off.p[NT] : 0;
+    a.pt_trace = E->pt_trace.p;
+    a.pts = E->points.dev.p;
+    a.scores = E->scores.dev.p;
+    a.trav = E->route.dev.p;
+    a.trav_off = E->tv_off.p;
+    a.span = E->sh_span.p;
+    a.poly = E->sh_poly.p;
+    a.poly_off = E->sh_off.p + T1;
+    const int64_t NI = a.n_points + a.n_trav;
+    if (NI + 1 >= (int64_t)INT32_MAX) {
+      *err = "trace attributes: too many items for one scan";
+      return OTM_EINVAL;
+    }
+    TRY(bind_buf(a.pt_off, E->at_pt_off, T1, err));
+    TRY(bind_buf(a.item_off, E->at_item_off, (size_t)NI + 1, err));
+    TRY(bind_buf(a.body_off, E->at_off, T1, err));
+    TRY(E->h_at_off.ensure(T1, err));
+    TRY(E->scan_tmp.ensure(scan_tmp_bytes(NI > NT ? NI : NT) + 256, err));
+    // the count pass, the two scans, one copy of the body offsets and the call's one wait
+    HIPCHK(hipMemsetAsync(a.item_off + NI, 0, sizeof *a.item_off, s));
+    HIPCHK(hipMemsetAsync(a.body_off + NT, 0, sizeof *a.body_off, s));
+    if (NT) {
+      if (mask & OTM_ATTR_POINTS) launch_attr_pt_off(a, s);
+      launch_attr_items(a, false, s);
+      if (NI) scan_i64(a.item_off, NI, E->scan_tmp.p, E->scan_tmp.cap(), s);
+      launch_attr_frame(a, false, s);
+      HIPCHK(hipGetLastError());
+      scan_i64(a.body_off, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    }
+    HIPCHK(hipMemcpyAsync(E->h_at_off.p, a.body_off, T1 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(wait_batch(E, s, E->last_P));
+    const int64_t bytes = E->h_at_off.p[NT];
+    TRY(E->attrs.dev.ensure((size_t)bytes + 1, err));
+    if (NT) {
+      a.blob = E->attrs.dev.p;
+      launch_attr_items(a, true, s);
+      launch_attr_frame(a, true, s);
+      HIPCHK(hipGetLastError());
+    }
+    E->attrs.n = bytes;
+  }
+  if (nt) *nt = NT;
+  if (nb) *nb = E->attrs.n;
+  return OTM_OK;
+}
+
+int engine_fetch_attributes(otm_engine* E, char* dst, int64_t cap, int64_t* body_off, int64_t* nb, std::string* err) {
+  TRY(engine_attributes_make(E, nullptr, nullptr, err));
+  if (body_off) std::memcpy(body_off, E->h_at_off.p, ((size_t)E->at_T + 1) * 8);
+  return engine_fetch_records(E, E->attrs, dst, cap, nb, err);
 }
 
 int engine_spill_stats(otm_engine* E, otm_spill_stats* out) {

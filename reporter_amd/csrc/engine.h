@@ -43,7 +43,7 @@ struct H2DOrder {
   bool own_queue = false;
 };
 // ---- Optional per-batch outputs: matched points (rule 7c), the matched route
-// (7d), match scores (7e), the matched shape (7f).  Each is a switch on the handle and one array of
+// (7d), match scores (7e), the matched shape (7f), trace attributes (7g).  Each is a switch on the handle and one array of
 // records that the last batch left, fetched any number of times until an
 // event ends them.
 //
@@ -54,6 +54,7 @@ enum RecEvent : unsigned {
   REC_BATCH_OUTPUTS = 2,  // ... reaches its optional outputs (a multi-device engine: joins its members')
   REC_BATCH_FAILED = 4,   // ... failed
   REC_OTHER_CALL = 8,     // a JSON-level call on this handle, wherever its batches run
+  REC_CALL_FAILED = 16,   // a binary-level call on this handle failed, wherever it failed (before its batch began too)
 };
 // An output's constants: the texts it answers through otm_last_error, and its
 // validity rule.
@@ -95,11 +96,26 @@ inline constexpr RecDesc kRecDesc<otm_shape_vertex>{
     "the matched shape is off (otm_set_shape)", "no batch has run with the matched shape on",
     "matched shape: a cap is below its count", "matched shape: an array is NULL with cap != 0",
     "engine or an argument is NULL", true, kRecDesc<otm_traversal>.ends};
+//  - trace attributes (rule 7g; their records are the blob's chars) restate the points, the scores, the
+//    route and the shape of one batch: they end with whichever of those ends first, which is the
+//    scores' rule, and with any binary-level call that fails, also one that its arguments failed before
+//    a batch began: after a failed call there is nothing to fetch.
+template <>
+inline constexpr RecDesc kRecDesc<char>{
+    "trace attributes are off (otm_set_attributes)", "no batch has run with trace attributes on",
+    "trace attributes: cap below the batch's byte count", "trace attributes: dst is NULL with cap != 0",
+    "engine or an argument is NULL", true,
+    kRecDesc<otm_point_score>.ends | kRecDesc<otm_traversal>.ends | REC_CALL_FAILED};
+static_assert(kRecDesc<char>.ends == (REC_BATCH_BEGINS | REC_BATCH_FAILED | REC_OTHER_CALL | REC_CALL_FAILED),
+              "the attributes' events");
 
 template <class Rec>
 struct BatchRecords {
   bool on = false;             // the handle's switch (otm_set_*)
-  int64_t n = -1;              // records of the last batch that left any (-1: none to fetch)
+  int64_t n = -1;              // records of the last batch that left any (-1: none to fetch).  For the
+                               // route and the shape n also says that the dense form / the arrays are
+                               // made, and trace attributes can make them with that output's switch off:
+                               // their fetches test `on` and tv_T / sh_T (the batch ran for them) first
   DevBuf<Rec> dev;             // ... on the device
   PinBuf<Rec> pin;             // the fetch's pinned staging
   std::vector<Rec> joined;     // a multi-device engine: its members' records in batch order
@@ -382,6 +398,21 @@ struct otm_engine {
   std::vector<otm_shape_span> g_sh_span;
   std::vector<char> g_sh_poly;
   std::vector<int64_t> g_sh_vtx_off, g_sh_trav_off, g_sh_poly_off;
+  // trace attributes (attributes.hip), made at the first size, fetch or device call of a batch from
+  // points.dev, scores.dev, route.dev / tv_off and sh_span / sh_poly: attrs.dev the blob (attrs.n its
+  // bytes, -1 until then; attrs.on: at_mask != 0).  at_T / at_P: the trace and point counts of the last
+  // batch that ran with the mask on (at_T -1: none), at_batch_mask the mask it ran with: a later
+  // otm_set_attributes changes the next batch's bodies, never the last one's.  at_off: body_off[at_T + 1], h_at_off its pinned
+  // copy; at_pt_off: the traces' point offsets; at_item_off: the items' scanned lengths; g_at_off: a
+  // multi-device engine's joined offsets (its blob: attrs.joined)
+  otm::BatchRecords<char> attrs;
+  uint32_t at_mask = 0;        // the handle's mask: what the next batch runs and leaves
+  uint32_t at_batch_mask = 0;  // the mask the last batch ran with (with at_T): what its bodies are made from
+  int32_t at_T = -1;
+  int64_t at_P = 0;
+  otm::DevBuf<int64_t> at_off, at_pt_off, at_item_off;
+  otm::PinBuf<int64_t> h_at_off;
+  std::vector<int64_t> g_at_off;
 };
 
 namespace otm {
@@ -467,6 +498,13 @@ int engine_fetch_traversals(otm_engine* E, otm_traversal* dst, int64_t cap, int6
 int engine_shape_make(otm_engine* E, otm_shape_sizes* sz, std::string* err);
 // ... then copies the parts of dst that are not null; OTM_EINVAL also when a cap is below its count
 int engine_fetch_shape(otm_engine* E, const otm_shape_out* dst, std::string* err);
+// trace attributes' preparation (rule 7g): once per batch the dense traversals and the matched shape for
+// the bits that need them, the count pass, its two scans, one copy of the body offsets and one wait,
+// then the write pass (E->attrs.dev, E->at_off, E->h_at_off; E->attrs.n).  *nt, *nb (may be null): the
+// trace count and the blob's bytes.  OTM_EINVAL when the mask is 0 or no batch ran with it on
+int engine_attributes_make(otm_engine* E, int64_t* nt, int64_t* nb, std::string* err);
+// ... then the blob to dst[cap] and the offsets to body_off (may be null); cap 0 with dst null only sizes
+int engine_fetch_attributes(otm_engine* E, char* dst, int64_t cap, int64_t* body_off, int64_t* nb, std::string* err);
 int engine_counters(otm_engine* E, otm_work_counters* out);
 // report() on the GPU over caller-supplied typed segments (otm_report_segments_device):
 // per trace t its points' times [trace_off[t], trace_off[t+1]) and segments

@@ -120,6 +120,8 @@ struct MemberOut {
   std::vector<otm_shape_span> sh_span;
   std::vector<char> sh_poly;
   std::vector<int64_t> sh_vtx_off, sh_trav_off, sh_poly_off;
+  std::vector<char> at_blob;           // (with the trace attributes' mask on) the member's bodies,
+  std::vector<int64_t> at_off;         // member trace i's at [at_off[i], at_off[i + 1])
   int rc = 0;
   std::string err;
 };
@@ -140,6 +142,8 @@ void run_member(otm_engine* M, MemberOut& o) {
     M->route.on = M->group->route.on;
     M->scores.on = M->group->scores.on;
     M->shape.on = M->group->shape.on;
+    M->attrs.on = M->group->attrs.on;
+    M->at_mask = M->group->at_mask;
     M->binary_batch = M->group->binary_batch;
   }
   otm_results r;
@@ -180,6 +184,14 @@ void run_member(otm_engine* M, MemberOut& o) {
                             z.n_traversals ? o.sh_span.data() : nullptr, z.n_traversals, o.sh_trav_off.data(),
                             z.n_bytes ? o.sh_poly.data() : nullptr,      z.n_bytes,      o.sh_poly_off.data()};
     o.rc = engine_fetch_shape(M, &dst, &o.err);
+  }
+  if (records_wanted(M, M->attrs) && !o.rc) {
+    int64_t nt = 0, nb = 0;
+    o.rc = engine_attributes_make(M, &nt, &nb, &o.err);
+    if (o.rc) return;
+    o.at_blob.resize((size_t)nb);
+    o.at_off.resize((size_t)nt + 1);
+    o.rc = engine_fetch_attributes(M, nb ? o.at_blob.data() : nullptr, nb, o.at_off.data(), &nb, &o.err);
   }
 }
 
@@ -320,6 +332,19 @@ int group_match(otm_engine* G, const otm_batch* b, const int32_t* shard, otm_res
       G->g_sh_poly_off[(size_t)t + 1] = (int64_t)G->g_sh_poly.size();
     }
     G->shape.joined_n = (int64_t)vtx.size();
+  }
+  // the members' trace attributes, likewise (a body names nothing outside its trace: only body_off is rebased)
+  if (records_wanted(G, G->attrs)) {
+    std::vector<char>& blob = G->attrs.joined;
+    blob.clear();
+    G->g_at_off.assign((size_t)nt + 1, 0);
+    for (int32_t t = 0; t < nt; ++t) {
+      const MemberOut& o = mo[(size_t)mem[(size_t)t]];
+      const size_t i = (size_t)pos[(size_t)t];
+      blob.insert(blob.end(), o.at_blob.begin() + o.at_off[i], o.at_blob.begin() + o.at_off[i + 1]);
+      G->g_at_off[(size_t)t + 1] = (int64_t)blob.size();
+    }
+    G->attrs.joined_n = (int64_t)blob.size();
   }
   out->n_traces = nt;
   out->n_segments = (int32_t)G->g_segs.size();

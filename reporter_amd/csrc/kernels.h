@@ -618,6 +618,31 @@ size_t resp_seg_scratch(int32_t ns, int32_t nw);
 void launch_resp_items(const RespIn& in, const RespWork& w, hipStream_t s);
 void launch_resp_len(const RespIn& in, const RespWork& w, hipStream_t s);
 void launch_resp_copy(const RespIn& in, const RespWork& w, const int64_t* boff, char* blob, hipStream_t s);
+// K7g: trace attributes (attributes.hip, DESIGN.md §3 rule 7g): one JSON body per trace from the
+// batch's optional outputs as they stand, made at the first size, fetch or device call of a batch.
+// Items are the matched point objects [0, n_points) and then the edge objects [n_points, n_points +
+// n_trav); a section that is off has no items (n_points or n_trav 0) and its inputs may be null.
+struct DevAttr {
+  uint32_t mask;              // OTM_ATTR_*
+  int32_t n_traces;
+  int64_t n_points, n_trav;   // items of the two kinds
+  const int32_t* pt_trace;    // [P] trace of point (DevWork's, as the batch left it)
+  const otm_matched_point* pts;
+  const otm_point_score* scores;  // (SCORES)
+  const otm_traversal* trav;      // dense, with trav_off (EDGES; trav_off also SHAPE)
+  const int64_t* trav_off;
+  const otm_shape_span* span;     // (EDGES and SHAPE)
+  const char* poly;               // (SHAPE) with poly_off
+  const int64_t* poly_off;
+  int64_t* pt_off;     // [T+1] the traces' point offsets (k_attr_pt_off)
+  int64_t* item_off;   // [items + 1] lengths, then the host's scan of them (element `items`: 0, then the total)
+  int64_t* body_off;   // [T+1] likewise, the bodies'
+  char* blob;          // [body_off[T]] (write pass only)
+};
+void launch_attr_pt_off(const DevAttr& a, hipStream_t s);
+// write false: the item lengths (items) and body lengths (frame); write true: the bytes
+void launch_attr_items(const DevAttr& a, bool write, hipStream_t s);
+void launch_attr_frame(const DevAttr& a, bool write, hipStream_t s);
 // exclusive scan helpers (in place over n+1 elements: out[n] = total)
 void scan_i64(int64_t* d, int64_t n, void* tmp, size_t tmp_bytes, hipStream_t s);
 // exclusive scans of three per-trace counts (n <= FETCH_SCAN_MAX) in one

@@ -125,7 +125,7 @@ class Results(object):
 class Engine(object):
     def __init__(self, config_path=None, graph_path=None, device=0, index_radius_m=None, grid_mult=None,
                  trans_lanes=None, devices=None, index_near_m=None, queue_speed_kph=None, matched_points=False,
-                 traversals=False, scores=False, shape=False, **meili):
+                 traversals=False, scores=False, shape=False, attributes=0, **meili):
         """Either a config file (valhalla.Configure-style) or a graph path.
         devices=[d0, d1, ...] makes a multi-device engine (otm_engine_create
         with ndev > 1): traces go to member murmur2(uuid) % ndev.
@@ -136,7 +136,9 @@ class Engine(object):
         scores: the per-point match scores of rule 7e (set_scores / scores;
         off: nothing changes).
         shape: the matched route's geometry of rule 7f (set_shape / shape;
-        off: nothing changes)."""
+        off: nothing changes).
+        attributes: the section mask of rule 7g's per-trace JSON bodies
+        (_lib.ATTR_*; True: every section; 0 or False: off, nothing changes)."""
         L = lib()
         self._tmp = None
         if config_path is None:
@@ -164,6 +166,8 @@ class Engine(object):
             self.set_scores(True)
         if shape:
             self.set_shape(True)
+        if attributes:
+            self.set_attributes(attributes)
 
     def members(self):
         """Member count: ndev of a multi-device engine, else 1."""
@@ -573,6 +577,40 @@ class Engine(object):
         dev, z = _lib.ShapeOut(), _lib.ShapeSizes()
         _check(lib().otm_shape_device(self.h, C.byref(dev), C.byref(z)))
         return dev, z
+
+    def set_attributes(self, mask):
+        """The trace attributes' section mask of this handle (otm_set_attributes):
+        _lib.ATTR_* bits, True for every section, 0 or False for off.  A
+        multi-device engine passes it to every member, a clone inherits it."""
+        mask = _lib.ATTR_ALL if mask is True else int(mask or 0)
+        _check(lib().otm_set_attributes(self.h, mask))
+
+    def attributes_info(self):
+        """The trace attributes' section mask (otm_attributes_info; 0: off)."""
+        m = C.c_uint32()
+        _check(lib().otm_attributes_info(self.h, C.byref(m)))
+        return m.value
+
+    def attributes(self):
+        """The trace attributes of the handle's last binary-level batch
+        (otm_attributes_size, otm_fetch_attributes): (blob, body_off) -- one
+        JSON body per trace in one bytes object, trace t's at
+        [body_off[t], body_off[t + 1]) (int64 array of n_traces + 1)."""
+        nt, nb = C.c_int64(), C.c_int64()
+        _check(lib().otm_attributes_size(self.h, C.byref(nt), C.byref(nb)))
+        blob = np.zeros(nb.value, dtype=np.uint8)
+        off = np.zeros(nt.value + 1, dtype=np.int64)
+        _check(lib().otm_fetch_attributes(self.h, blob.ctypes.data if nb.value else None, nb.value, off.ctypes.data,
+                                          C.byref(nb)))
+        return blob.tobytes(), off
+
+    def attributes_device(self):
+        """The last batch's trace attributes in this GPU's HBM
+        (otm_attributes_device; a one-device engine's, valid until its next
+        batch): (blob pointer, body_off pointer, n_traces, n_bytes)."""
+        dev, off, nt, nb = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+        _check(lib().otm_attributes_device(self.h, C.byref(dev), C.byref(off), C.byref(nt), C.byref(nb)))
+        return dev.value or 0, off.value or 0, nt.value, nb.value
 
     def set_counting(self, on):
         _check(lib().otm_set_counting(self.h, 1 if on else 0))
