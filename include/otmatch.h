@@ -919,6 +919,25 @@ typedef struct otm_spill_stats {
  * clone keeps its own, and grows its own on-demand tier tables). */
 int otm_get_spill_stats(otm_engine* eng, otm_spill_stats* out);
 
+/* Tiers on demand: five groups of kernel launches exist only
+ * for work an earlier kernel hands them through a device list -- bit 0 the
+ * candidate HBM tier, bit 1 the online transition tiers, bit 2 the online
+ * route tiers, bit 3 the Viterbi list passes, bit 4 the large segment plan.
+ * A batch context stops launching a group whose list stayed empty two
+ * completed batches in a row; a batch that then needs it is run again with
+ * the group live, and the group stays live for the context's life
+ * (OTM_TIERS_ALWAYS=1 in the environment: every group is always launched).
+ * Read-only: *dormant_mask the groups this handle's own context does not
+ * launch now, *dispatches the stream dispatches (kernels, scans' two, memsets)
+ * of its last batch's final attempt, the optional outputs' kernels apart.
+ * Either pointer may be NULL. */
+#define OTM_TIER_CAND_BIG 1
+#define OTM_TIER_TRANS_ONLINE 2
+#define OTM_TIER_ROUTE_ONLINE 4
+#define OTM_TIER_VIT_LISTS 8
+#define OTM_TIER_SEG_LARGE 16
+int otm_get_tiers(otm_engine* eng, int32_t* dormant_mask, int32_t* dispatches);
+
 /* Stage outputs of the last batch, for parity tests (device -> host copy).
  * what: 0 ncand i32[P], 1 cand_edge i32[P*KMAX], 2 cand_off f32[P*KMAX],
  * 3 cand_emis f32[P*KMAX], 4 trans_off i64[P+1], 5 trans f32[total],

@@ -283,6 +283,7 @@ def _declare(L):
         "otm_get_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),
         "otm_kernel_name": (C.c_char_p, [C.c_int]),
         "otm_get_spill_stats": (C.c_int, [vp, C.POINTER(SpillStats)]),
+        "otm_get_tiers": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "otm_debug_fetch": (C.c_int, [vp, C.c_int, vp, sz, psz]),
         "otm_kmax": (C.c_int, []),
         "otm_debug_py_repr": (C.c_int, [C.c_double, C.c_char_p]),

@@ -2678,6 +2678,19 @@ int otm_get_spill_stats(otm_engine* E, otm_spill_stats* out) {
   return otm::engine_spill_stats(E, out) ? fail(OTM_EDEVICE, "spill stats copy failed") : OTM_OK;
 }
 
+static_assert(OTM_TIER_CAND_BIG == otm::TIER_CAND_BIG && OTM_TIER_TRANS_ONLINE == otm::TIER_TRANS_ONLINE &&
+                  OTM_TIER_ROUTE_ONLINE == otm::TIER_ROUTE_ONLINE && OTM_TIER_VIT_LISTS == otm::TIER_VIT_LISTS &&
+                  OTM_TIER_SEG_LARGE == otm::TIER_SEG_LARGE,
+              "tier group bits");
+int otm_get_tiers(otm_engine* E, int32_t* dormant_mask, int32_t* dispatches) {
+  if (!E) return fail(OTM_EINVAL, "engine is NULL");
+  if (!E->members.empty()) E = E->members[0];  // the first member (others: otm_engine_member)
+  std::lock_guard<std::mutex> lk(E->mu);
+  if (dormant_mask) *dormant_mask = E->tier_dormant;
+  if (dispatches) *dispatches = E->last_dispatches;
+  return OTM_OK;
+}
+
 int otm_debug_fetch(otm_engine* E, int what, void* dst, size_t bytes, size_t* needed) {
   if (!E) return fail(OTM_EINVAL, "engine is NULL");
   if (!E->members.empty()) E = E->members[0];  // the first member (others: otm_engine_member)

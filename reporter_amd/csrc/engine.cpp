@@ -748,10 +748,14 @@ static int bind_point_work(otm_engine* E, int64_t NP, int32_t NT, DevWork& w, st
 }
 
 // The spatial work order's arrays (tile_cnt null: no order this batch).
-static int bind_order(otm_engine* E, int64_t NP, bool ordered, DevOrder& ord, std::string* err) {
+// The tile counts start as zeros and k_order_plan, their one reader, leaves
+// them as zeros for the next batch.
+static int bind_order(otm_engine* E, int64_t NP, bool ordered, DevOrder& ord, hipStream_t s, std::string* err) {
   const size_t Pn = (size_t)NP + 1;
+  bool fresh;
   TRY(bind_buf(ord.tile, E->ord_tile, Pn, err));
-  TRY(bind_buf(ord.tile_cnt, E->ord_cnt, ORDER_TILES, err));
+  TRY(bind_buf(ord.tile_cnt, E->ord_cnt, ORDER_TILES, err, &fresh));
+  if (fresh) HIPCHK(hipMemsetAsync(E->ord_cnt.p, 0, E->ord_cnt.bytes(), s));
   TRY(bind_buf(ord.cursor, E->ord_cursor, ORDER_TILES, err));
   TRY(bind_buf(ord.grp, E->ord_grp, ORDER_GROUPS + 1, err));
   TRY(bind_buf(ord.item, E->ord_item, Pn, err));
@@ -842,19 +846,27 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     dp.cand_chunk = ch < 1 ? 1 : (ch > 64 ? 64 : ch);
   }
   w.ctr = E->counting ? E->ctr.p : nullptr;
-  if (E->counting && from == RESUME_ALL) HIPCHK(hipMemsetAsync(E->ctr.p, 0, sizeof(DevCounters), s));
+  w.dormant = E->tier_dormant;  // (kernels.h TierGroup: those groups' launches are left out below)
+  E->last_dispatches = 0;
+  if (E->counting && from == RESUME_ALL) {
+    HIPCHK(hipMemsetAsync(E->ctr.p, 0, sizeof(DevCounters), s));
+    E->last_dispatches += 1;
+  }
   // the counters' and abort flag's reset, the spill snapshots and the
   // transition capacity check ride in K1, K3, K4, K5 and K7 (kernels.h CtrSlot)
   Marks mk;
   mk.ev = E->timing ? E->kev : nullptr;
-  TRY(bind_order(E, NP, dp.order_mask != 0, w.ord, err));
+  mk.dispatches = &E->last_dispatches;
+  TRY(bind_order(E, NP, dp.order_mask != 0, w.ord, s, err));
   if (from == RESUME_ALL) {
-    launch_columns(E->g, b, dp, w, s, mk);
+    // (DevOut::seg_base exists by now: K1 zeroes it per trace; bind_out finds it at the same size)
+    int64_t* seg_base = nullptr;
+    TRY(bind_buf(seg_base, E->seg_ub, (size_t)NT + 1, err));
+    launch_columns(E->g, b, dp, w, seg_base, s, mk);
     if (dp.order_mask) {
       launch_order(b, w, s, mk);
-    } else if (E->timing) {
-      mk.begin(KN_ORDER, s);
-      mk.end(KN_ORDER, s);
+    } else {
+      mk.skip(KN_ORDER, s);
     }
   }
   TRY(ensure_cand(E, w, err));
@@ -865,6 +877,7 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     launch_links(b, dp, w, s, mk);
     mk.begin(KN_SCAN_TRANS, s);
     scan_i64(w.trans_off, NP, E->scan_tmp.p, E->scan_tmp.cap(), s);
+    mk.count(2);  // (the library's scan is an init and a scan kernel)
     mk.end(KN_SCAN_TRANS, s);
   }
   TRY(bind_trans(E, w, s, err));
@@ -893,10 +906,13 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
     o.bin_kph = H->bin_kph;
     o.pairs = H->pairs_tab;  // (key null: no pair window)
   }
-  HIPCHK(hipMemsetAsync(o.seg_base, 0, ((size_t)NT + 1) * sizeof *o.seg_base, s));
+  // seg_base is zero here: K1 zeroed it, and on a resumed attempt, where K1 does not run again, the
+  // aborted attempt's k_seg_bound returned before its atomics (every abort that leads to a resume is
+  // raised before K7a; the one raised after it, the large segment plan's wake, redoes the batch whole)
   launch_seg_bound(E->g, b, dp, w, o.seg_base, s, mk);
   mk.begin(KN_SEG_SCAN, s);
   scan_i64(o.seg_base, NT, E->scan_tmp.p, E->scan_tmp.cap(), s);
+  mk.count(2);
   mk.end(KN_SEG_SCAN, s);
   launch_segments(E->g, b, w, o, s, mk);
   // K7b (DESIGN.md §3 rule 7b): only with a queue threshold; outside the timing marks
@@ -948,8 +964,35 @@ static int engine_match_once(otm_engine* E, const DevBatch& b, hipStream_t s, st
   return OTM_OK;
 }
 
+// What a completed batch teaches this context about its on-demand groups
+// (kernels.h TierGroup): a group whose first list stayed empty TIER_QUIET
+// batches in a row goes dormant; one that had work starts its count again.
+// A group that was ever needed while dormant (tiers_wake) stays live.
+static void tiers_learn(otm_engine* E, int32_t idle) {
+  if (E->tiers_always) return;
+  for (int g = 0; g < TIER_GROUPS; ++g) {
+    const int32_t bit = 1 << g;
+    if (E->tier_woken & bit) continue;
+    E->tier_quiet[g] = (idle & bit) ? E->tier_quiet[g] + 1 : 0;
+    if (E->tier_quiet[g] >= TIER_QUIET) E->tier_dormant |= bit;
+  }
+}
+// (A batch whose transitions the route index cannot answer needs the online
+// route tiers for the same steps: they wake together, in one extra attempt.)
+static void tiers_wake(otm_engine* E, int32_t groups) {
+  if (groups & TIER_TRANS_ONLINE) groups |= TIER_ROUTE_ONLINE;
+  E->tier_woken |= groups;
+  E->tier_dormant &= ~groups;
+}
+
 int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* err) {
   if (!s) s = E->stream;
+  if (!E->tiers_read) {
+    // OTM_TIERS_ALWAYS=1: every on-demand group is launched every batch (tests, A/B runs)
+    E->tiers_read = true;
+    const char* v = std::getenv("OTM_TIERS_ALWAYS");
+    E->tiers_always = v && *v && *v != '0';
+  }
   const int64_t NP = b.n_points;
   // A tier that ran out of HBM fails its overflowing traces for this batch
   // only: the next batch tries to grow it again (the growth cap, by contrast,
@@ -977,21 +1020,35 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     // the one synchronisation of a batch: did every capacity hold?
     // (gathered on the device, one copy into pinned memory)
     TRY(E->h_status.ensure(1, err));
+    // (k_status writes the device copy and the page-locked host record: no copy command)
     BatchStatus* dst = &E->snap.p->status;
-    launch_status(E->abort_flag.p, E->trans_off.p + NP, E->counters_i32.p, dst, s);
-    HIPCHK(hipMemcpyAsync(E->h_status.p, dst, sizeof(BatchStatus), hipMemcpyDeviceToHost, s));
+    launch_status(E->abort_flag.p, E->trans_off.p + NP, E->counters_i32.p, &E->snap.p->stage[0][0], dst,
+                  E->h_status.p, s);
+    E->last_dispatches += 1;
     HIPCHK(wait_batch(E, s, NP));
-    const BatchStatus st = *E->h_status.p;
+    BatchStatus st = *E->h_status.p;
     const int32_t ab = st.abort;
     const int64_t ttotal = st.ttotal;
     E->last_trans = ttotal;
     E->last_attempts = attempt + 1;
-    if (!ab) break;
+    if (!ab) {
+      tiers_learn(E, st.tier_idle);
+      break;
+    }
     if (attempt == 16) {
       *err = "batch capacities could not be sized";
       return OTM_EDEVICE;
     }
     if (ttotal > E->trans_cap) E->trans_cap = ttotal + ttotal / 4 + 4096;
+    // A dormant group was needed: live from now on, and the batch runs again
+    // -- whole, but for the candidate HBM tier: the candidate kernels never
+    // stop on the abort flag, so its list is complete and every later stage
+    // returned at once, which is the state its table growth resumes from; and
+    // a tier with no tables yet would only ask for them in the next attempt.
+    const int32_t woke = st.tier_wake & TIER_ALL;
+    if (woke) tiers_wake(E, woke);
+    const bool woke_cand_only = woke == TIER_CAND_BIG && !st.pool_over;
+    if (woke_cand_only && E->cand_log2 == 0 && !E->cand_final) st.grow |= GROW_CAND;
     if (st.grow & GROW_HUGE) {
       // a search outgrew the huge tier's tables (or found none): 4x the slots,
       // or, past the cap or out of HBM, the overflowing traces fail alone
@@ -1039,10 +1096,16 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
     // that stage's boundary (A after the candidates, B after the transitions,
     // C after the routes), so the resumed kernels retake the same snapshots.
     const char* nr = std::getenv("OTM_NO_RESUME");  // A/B knob: every redo whole (rounds 1-5)
-    const bool whole = ttotal > E->trans_cap || st.pool_over || !(st.grow & (GROW_HUGE | GROW_CAND)) ||
+    // (A transition total past the matrices' capacity, grown above, meets a grow flag or a wake only when
+    // the abort was raised in the candidate stage -- the first transition kernel stops everything after it
+    // on that overflow -- and the attempt resumed there binds the larger matrices and runs k_links and the
+    // transition stage again.  Alone it has no grow flag and redoes the batch whole.)
+    const bool whole = st.pool_over ||
+                       !((st.grow & (GROW_HUGE | GROW_CAND)) || woke_cand_only) || (woke && !woke_cand_only) ||
                        (nr && *nr && *nr != '0');
     from = whole ? RESUME_ALL
-                 : (st.grow & GROW_CAND) ? RESUME_CAND_BIG : (st.route_huge ? RESUME_ROUTE_HUGE : RESUME_TRANS_HUGE);
+                 : ((st.grow & GROW_CAND) || woke_cand_only) ? RESUME_CAND_BIG
+                 : (st.route_huge ? RESUME_ROUTE_HUGE : RESUME_TRANS_HUGE);
     if (from != RESUME_ALL) {
       const SnapId snap = from == RESUME_CAND_BIG ? SNAP_AFTER_CAND
                                                   : (from == RESUME_TRANS_HUGE ? SNAP_AFTER_TRANS : SNAP_AFTER_ROUTE);
@@ -1051,6 +1114,7 @@ int engine_match(otm_engine* E, const DevBatch& b, hipStream_t s, std::string* e
                             hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemsetAsync(ctr + CTR_GROW_HUGE, 0, 4, s));
       HIPCHK(hipMemsetAsync(ctr + CTR_GROW_CAND, 0, 4, s));
+      HIPCHK(hipMemsetAsync(ctr + CTR_TIER_WAKE, 0, 4, s));
       HIPCHK(hipMemsetAsync(E->abort_flag.p, 0, 4, s));
       E->last_resumes += 1;
     }

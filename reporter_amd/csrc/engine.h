@@ -216,6 +216,13 @@ struct otm_engine {
   int32_t huge_final = 0, cand_final = 0;  // the tier's tables cannot grow: overflows fail their traces
   int32_t last_attempts = 0;  // runs of the last batch (otm_spill_stats::attempts)
   int32_t last_resumes = 0;   // ... of them resumed from a grown tier (otm_spill_stats::resumed)
+  // tiers on demand (kernels.h TierGroup; engine.cpp tiers_learn): this context's dormant groups, the
+  // groups a batch needed while dormant (live for good), each group's run of quiet batches, the
+  // OTM_TIERS_ALWAYS switch, and the stream dispatches of the last attempt's pipeline (otm_get_tiers)
+  int32_t tier_dormant = 0, tier_woken = 0;
+  int32_t tier_quiet[otm::TIER_GROUPS] = {};
+  bool tiers_read = false, tiers_always = false;
+  int32_t last_dispatches = 0;
   // spatial work order (DevOrder)
   otm::DevBuf<uint16_t> ord_tile;
   otm::DevBuf<int32_t> ord_cnt, ord_cursor, ord_grp, ord_item;

@@ -268,6 +268,8 @@ struct DevCounters {
 //   CTR_CAND_BIG       3     candidate wave tier -> HBM tier (k_candidates<false> -> <true>)
 //   CTR_GROW_CAND      -     flag: the candidate HBM tier needs (larger) tables (k_candidates)
 //   CTR_VIT_WAVE       2     Viterbi row form or 16 lanes -> wave form (launch_viterbi)
+//   CTR_TIER_WAKE      -     TierGroup bits: a kernel pushed onto a list whose drainers were not launched
+//                            (tier_wake below; the host makes the groups live and runs the batch again)
 //
 // The Viterbi counts are per batch, not per stage: SNAP_AFTER_TRANS is taken
 // (and the per-stage slots reset) by one thread of the first Viterbi launch,
@@ -290,10 +292,32 @@ enum CtrSlot : int {
   CTR_CAND_BIG = 24,
   CTR_GROW_CAND = 25,
   CTR_VIT_WAVE = 26,
+  CTR_TIER_WAKE = 27,
 };
 constexpr int CTR_STAGE_WORDS = 16;   // per stage: snapshot and reset
 constexpr int CTR_ZEROED_WORDS = 32;  // per stage + per batch: zeroed by K1
 constexpr int CTR_WORDS = 64;         // allocated
+// ---- Tiers on demand.  Five launch groups exist only for work that an earlier
+// kernel pushes onto a device list, and on most workloads those lists stay
+// empty batch after batch: each launch then starts its blocks to read a zero
+// and costs its 4-5 us on the stream.  Every batch context keeps a mask of
+// live groups (otm_engine::tier_dormant, engine.cpp tiers_learn): a group
+// whose first list stayed empty for TIER_QUIET completed batches goes dormant
+// and is not launched.  DevWork::dormant tells the kernels; one that pushes
+// onto a dormant group's list also sets its bit in CTR_TIER_WAKE and the abort
+// flag (tier_wake), every later kernel returns at once as after a capacity
+// overflow, and the host makes the group live for the rest of the context's
+// life and runs the batch again.  OTM_TIERS_ALWAYS=1 keeps every group live.
+enum TierGroup : int {
+  TIER_CAND_BIG = 1,      // k_candidates<true>            first list CTR_CAND_BIG
+  TIER_TRANS_ONLINE = 2,  // k_transitions<0..2>           first list CTR_INDEX_MISS (transition stage)
+  TIER_ROUTE_ONLINE = 4,  // k_route<0..2>                 first list CTR_INDEX_MISS (route stage)
+  TIER_VIT_LISTS = 8,     // Viterbi list passes           lists CTR_VIT_WAVE, CTR_VIT_16
+  TIER_SEG_LARGE = 16,    // k_segments' large plan        list CTR_SEG_LARGE
+  TIER_ALL = 31,
+};
+constexpr int TIER_GROUPS = 5;
+constexpr int TIER_QUIET = 2;  // completed batches with an empty first list before a group goes dormant
 enum SnapId : int { SNAP_AFTER_CAND = 0, SNAP_AFTER_TRANS = 1, SNAP_AFTER_ROUTE = 2, SNAP_COUNT = 3 };
 // which of DevWork::spill_list1..3 the count in slot c belongs to (0: c counts no list)
 constexpr int ctr_list(CtrSlot c) {
@@ -312,7 +336,7 @@ static_assert(ctr_per_stage(CTR_UNUSED) && ctr_per_stage(CTR_POOL_USED) && ctr_p
               "per-stage slots lie in the snapshot range");
 static_assert(ctr_per_batch(CTR_VIT_16) && ctr_per_batch(CTR_TRANS_HUGE) && ctr_per_batch(CTR_ROUTE_HUGE) &&
                   ctr_per_batch(CTR_GROW_HUGE) && ctr_per_batch(CTR_CAND_BIG) && ctr_per_batch(CTR_GROW_CAND) &&
-                  ctr_per_batch(CTR_VIT_WAVE),
+                  ctr_per_batch(CTR_VIT_WAVE) && ctr_per_batch(CTR_TIER_WAKE),
               "per-batch slots lie past the snapshot range, within what K1 zeroes");
 
 // per-point / per-trace work arrays of one batch (device pointers)
@@ -348,6 +372,7 @@ struct DevWork {
   int32_t* path_len;     // [P]
   int32_t* path_pool;    // [pool_cap]
   int32_t pool_cap;
+  int32_t dormant;       // TierGroup bits: groups not launched this attempt (in pool_cap's padding: no field moves)
   int32_t* trace_err;    // [T]
   int32_t* spill_list1;    // [P] a stage's first spill list (CtrSlot above: who fills and drains it when)
   int32_t* spill_list2;    // [P] ... its second
@@ -477,6 +502,15 @@ enum KernelId {
 extern const char* const kKernelNames[KN_COUNT];
 struct Marks {
   hipEvent_t* ev = nullptr;
+  int32_t* dispatches = nullptr;  // the attempt's stream dispatches, counted by the launchers (otm_get_tiers)
+  void count(int n = 1) const {
+    if (dispatches) *dispatches += n;
+  }
+  // an empty span: the slot of a kernel that was not launched keeps its name and reads ~0
+  void skip(int k, hipStream_t s) const {
+    begin(k, s);
+    end(k, s);
+  }
   void begin(int k, hipStream_t s) const {
     if (ev) (void)hipEventRecord(ev[2 * k], s);
   }
@@ -486,8 +520,9 @@ struct Marks {
 };
 
 // ---- launch wrappers (kernels.hip)
-void launch_columns(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
-                    const Marks& mk);
+// seg_base: DevOut::seg_base [T+1], which K1 zeroes per trace for K7a (launch_seg_bound)
+void launch_columns(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* seg_base,
+                    hipStream_t s, const Marks& mk);
 // Where a batch resumes after a tier's tables grew (engine_match): the stages
 // before the tier that overflowed kept their results, so only that tier and
 // what follows it run again (RESUME_ALL: the whole batch).
@@ -545,7 +580,7 @@ void launch_shape(const DevGraph& g, int32_t n_traces, const int64_t* seg_base, 
 void launch_report(const DevBatch& b, const DevReportCfg& rc, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk);
 // spatial work order: tile counts, plan (group cuts), scatter of the columns
 void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk);
-// K7a: each trace's segment bound added into tb[T] (zeroed by the caller;
+// K7a: each trace's segment bound added into tb[T] (zeroed by K1;
 // scanned into DevOut::seg_base) and the interpolated points placed
 void launch_seg_bound(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* tb, hipStream_t s,
                       const Marks& mk);
@@ -570,18 +605,22 @@ struct BatchStatus {
   int64_t ttotal;
   int32_t pool_used, pool_over;  // CTR_POOL_USED, CTR_POOL_OVER
   int32_t route_huge;   // CTR_ROUTE_HUGE: the route stage reached its huge tier (else the transition stage did)
+  int32_t tier_idle;    // TierGroup bits: the group's first list stayed empty this batch
+  int32_t tier_wake;    // CTR_TIER_WAKE: dormant groups this attempt needed
+  int32_t pad;
 };
 // otm_engine::snap: the spill snapshots (DevWork::snap), then k_status's staging area
 struct SnapBuf {
   int32_t stage[SNAP_COUNT][CTR_STAGE_WORDS];
   BatchStatus status;
 };
-static_assert(offsetof(SnapBuf, status) == 192 && sizeof(SnapBuf) == 192 + 32, "snapshot buffer layout");
+static_assert(offsetof(SnapBuf, status) == 192 && sizeof(SnapBuf) == 192 + 40, "snapshot buffer layout");
 // otm_match_compact's inputs widened on the device (time = base + delta, accuracy as float)
 void launch_expand_compact(const int64_t* trace_off, const int64_t* tbase, const int32_t* dt, const int16_t* acc16,
                            double* time, float* acc, int32_t n_traces, hipStream_t s);
-void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out,
-                   hipStream_t s);
+// out: the device copy; host: the same record in page-locked host memory, written by the kernel itself
+void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, const int32_t* snap,
+                   BatchStatus* out, BatchStatus* host, hipStream_t s);
 void launch_row_pack(const int32_t* row_cnt, const int64_t* row_off, IdxRow* rows, int32_t n, hipStream_t s);
 // an index's per-edge source records from its packed rows and the graph's {from, length} pairs
 void launch_src_pack(const DevGraph& g, const IdxRow* rows, SrcRec* src, hipStream_t s);

@@ -312,10 +312,22 @@ __device__ __forceinline__ void fold_snap(DevWork& w, int k, bool reset) {
     if (reset) w.counters_i32[t] = 0;
   }
 }
-// one lane: p onto the list that slot C counts
-template <CtrSlot C>
+// one lane, about to push onto a list that group G's kernels drain: when the
+// group is dormant (kernels.h TierGroup) nothing will drain it this attempt,
+// so the batch aborts and says which group it needs
+template <int G>
+__device__ __forceinline__ void tier_wake(const DevWork& w) {
+  if (G != 0 && (w.dormant & G)) {
+    atomicOr(&w.counters_i32[CTR_TIER_WAKE], G);
+    *w.abort = 1;
+  }
+}
+// one lane: p onto the list that slot C counts (G: the TierGroup that drains
+// it when that group is launched on demand, 0: drained by a kernel that always runs)
+template <CtrSlot C, int G = 0>
 __device__ __forceinline__ void spill_push(const DevWork& w, int32_t p) {
   const SpillRef s = spill_of<C>(w);
+  tier_wake<G>(w);
   s.list[atomicAdd(s.count, 1)] = p;
 }
 // every transition kernel's first test: the matrices' total against the
@@ -396,8 +408,10 @@ __device__ __forceinline__ void wave_agg_count(int32_t* ctr, int key, bool activ
 }
 
 // one block: exclusive scan of the tile counts (Hilbert order), cursors, and
-// the 8 group cuts at the tile boundaries nearest k/8 of the columns
-__global__ __launch_bounds__(1024) void k_order_plan(const int32_t* tile_cnt, int32_t* cursor, int32_t* grp) {
+// the 8 group cuts at the tile boundaries nearest k/8 of the columns.  Having
+// read the counts it zeroes them for the next batch's K1 (they start as zeros
+// at allocation, engine.cpp bind_order), so no batch pays a memset for them.
+__global__ __launch_bounds__(1024) void k_order_plan(int32_t* tile_cnt, int32_t* cursor, int32_t* grp) {
   __shared__ int32_t part[1024];
   __shared__ int32_t cut[ORDER_GROUPS + 1];
   constexpr int PER = ORDER_TILES / 1024;
@@ -432,6 +446,8 @@ __global__ __launch_bounds__(1024) void k_order_plan(const int32_t* tile_cnt, in
     run += v[k];
   }
   __syncthreads();
+  // (every thread has read its neighbour's last count by now)
+  for (int k = 0; k < PER; ++k) tile_cnt[tid * PER + k] = 0;
   if (tid == 0) {
     grp[0] = 0;
     int32_t prev = 0;
@@ -469,7 +485,8 @@ __global__ __launch_bounds__(256) void k_order_scatter(DevBatch b, DevWork w, co
 #define OTM_COL_PTS 256
 #endif
 constexpr int COL_PTS = OTM_COL_PTS;
-__global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParams P, DevWork w) {
+// seg_base: DevOut::seg_base [T+1], zeroed here per trace for K7a's sums (it was a memset of its own)
+__global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParams P, DevWork w, int64_t* seg_base) {
   __shared__ float sLat[COL_PTS], sLon[COL_PTS], sGc[COL_PTS];
   __shared__ int32_t sPrev[COL_PTS];
   __shared__ uint8_t sCol[COL_PTS];
@@ -478,6 +495,7 @@ __global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParam
     // the batch's tier counters (per stage and per batch) and abort flag start at zero
     if (lane < CTR_ZEROED_WORDS) w.counters_i32[lane] = 0;
     if (lane == 0) *w.abort = 0;
+    if (lane == 0) seg_base[b.n_traces] = 0;  // (the element the scan leaves the bounds' total in)
   }
   for (int32_t t = blockIdx.x; t < b.n_traces; t += gridDim.x) {
     const int64_t a = b.trace_off[t], e = b.trace_off[t + 1];
@@ -579,6 +597,7 @@ __global__ __launch_bounds__(TB) void k_columns(DevGraph g, DevBatch b, DevParam
     }
     if (lane == 0) {
       w.trace_err[t] = 0;
+      seg_base[t] = 0;  // K7a adds the trace's segment bound here
       if (w.ctr) {
         cadd(&w.ctr->points, (unsigned long long)n);
         cadd(&w.ctr->columns, (unsigned long long)ncols);
@@ -1119,7 +1138,7 @@ __global__ __launch_bounds__(TB) void k_candidates(DevGraph g, DevBatch b, DevPa
     if (s_over) {
       if (lane == 0) {
         if (!BIG) {
-          spill_push<CTR_CAND_BIG>(w, (int32_t)p);  // to the HBM tables
+          spill_push<CTR_CAND_BIG, TIER_CAND_BIG>(w, (int32_t)p);  // to the HBM tables
         } else if (w.cand_final) {
           // the tables are as large as they get: this probe's trace fails
           // alone (500, OTM_TERR_CAND_OVERFLOW), the batch goes on
@@ -1277,14 +1296,33 @@ __global__ __launch_bounds__(256) void k_links(DevBatch b, DevParams P, DevWork 
 // transition total, path-pool counters.  A single-wave kernel rather than
 // memcpy commands: each runtime copy is its own blit dispatch (3.5-8 us each
 // on the stream).
-__global__ void k_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out) {
+// It goes to the device copy (engine_match resumes from the snapshots beside
+// it) and straight into the host's page-locked record, which the device sees:
+// the kernel's end makes its stores visible to the host that waits for the
+// stream, as a copy command's would be, without the copy's dispatch.
+// tier_idle: which on-demand groups' first lists stayed empty (kernels.h
+// TierGroup) -- the transition and route stages' CTR_INDEX_MISS from their
+// snapshots, the per-batch counts and CTR_SEG_LARGE (counted after the last
+// snapshot) from the counters themselves.
+__global__ void k_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, const int32_t* snap,
+                         BatchStatus* out, BatchStatus* host) {
   if (threadIdx.x == 0) {
-    out->abort = *abort;
-    out->grow = (counters[CTR_GROW_HUGE] != 0 ? GROW_HUGE : 0) | (counters[CTR_GROW_CAND] != 0 ? GROW_CAND : 0);
-    out->ttotal = *ttotal;
-    out->pool_used = counters[CTR_POOL_USED];
-    out->pool_over = counters[CTR_POOL_OVER];
-    out->route_huge = counters[CTR_ROUTE_HUGE];
+    BatchStatus st;
+    st.abort = *abort;
+    st.grow = (counters[CTR_GROW_HUGE] != 0 ? GROW_HUGE : 0) | (counters[CTR_GROW_CAND] != 0 ? GROW_CAND : 0);
+    st.ttotal = *ttotal;
+    st.pool_used = counters[CTR_POOL_USED];
+    st.pool_over = counters[CTR_POOL_OVER];
+    st.route_huge = counters[CTR_ROUTE_HUGE];
+    st.tier_idle = (counters[CTR_CAND_BIG] == 0 ? TIER_CAND_BIG : 0) |
+                   (snap[CTR_STAGE_WORDS * SNAP_AFTER_TRANS + CTR_INDEX_MISS] == 0 ? TIER_TRANS_ONLINE : 0) |
+                   (snap[CTR_STAGE_WORDS * SNAP_AFTER_ROUTE + CTR_INDEX_MISS] == 0 ? TIER_ROUTE_ONLINE : 0) |
+                   (counters[CTR_VIT_WAVE] == 0 && counters[CTR_VIT_16] == 0 ? TIER_VIT_LISTS : 0) |
+                   (counters[CTR_SEG_LARGE] == 0 ? TIER_SEG_LARGE : 0);
+    st.tier_wake = counters[CTR_TIER_WAKE];
+    st.pad = 0;
+    *out = st;
+    *host = st;
   }
 }
 
@@ -1882,7 +1920,7 @@ __global__ __launch_bounds__(TB, OTM_TRANS_WAVES) void k_trans_sub(DevGraph g, D
       }
     }
     const bool spill = (__ballot(bad) & smask) != 0ull;
-    if (spill && act && sl == 0) spill_push<CTR_INDEX_MISS>(w, (int32_t)p);
+    if (spill && act && sl == 0) spill_push<CTR_INDEX_MISS, TIER_TRANS_ONLINE>(w, (int32_t)p);
     act = act && !spill;
     // an inactive group (out of range, unlinked, wide-listed, spilled) has no pairs
     const int npair_g = act ? Kq * Kp : 0;
@@ -2056,7 +2094,7 @@ __global__ __launch_bounds__(256, OTM_ROUTE_WAVES) void k_route_index(DevGraph g
       sv = idx_find(Xc.slot, Rw, dst_key(g, ej, oj), lab);
     }
     if (sv < 0 || idx_slot_cost(lab) > cq) {
-      spill_push<CTR_INDEX_MISS>(w, (int32_t)p);
+      spill_push<CTR_INDEX_MISS, TIER_ROUTE_ONLINE>(w, (int32_t)p);
       continue;
     }
     // the path: the label's predecessor slots in the row, back to the first
@@ -2797,7 +2835,10 @@ __global__ __launch_bounds__(TB, G == 8 ? OTM_VG8_WAVES : 3) void k_viterbi_g(De
       take = ((__ballot(wide) >> gb) & gmask) == 0ull;
     }
     if (act && !take) {
-      if (j == 0) rej[atomicAdd(rej_n, 1)] = t;
+      if (j == 0) {
+        tier_wake<TIER_VIT_LISTS>(w);
+        rej[atomicAdd(rej_n, 1)] = t;
+      }
       act = false;
     }
     if (!act) n = 0;
@@ -3191,7 +3232,10 @@ __global__ __launch_bounds__(TB, OTM_VR_WAVES) void k_viterbi_row(DevBatch b, De
       take = ((__ballot(wide) >> gb) & 0xFFFFull) == 0ull;
     }
     if (act && !take) {
-      if (j == 0) rej[atomicAdd(rej_n, 1)] = t;
+      if (j == 0) {
+        tier_wake<TIER_VIT_LISTS>(w);
+        rej[atomicAdd(rej_n, 1)] = t;
+      }
       act = false;
     }
     if (!act) n = 0;
@@ -4021,8 +4065,11 @@ __global__ __launch_bounds__(TB, (PT <= 128 ? 4 : 2)) void k_segments(DevGraph g
     }
     if (n > PT) {
       if (lane == 0) {
-        if (spill) spill[atomicAdd(spill_n, 1)] = t;
-        else segments_trace<true>(g, w, o, t, n, base, SegSrcGlobal{&g, &b, &w, a});
+        if (spill) {
+          tier_wake<TIER_SEG_LARGE>(w);
+          spill[atomicAdd(spill_n, 1)] = t;
+        } else
+          segments_trace<true>(g, w, o, t, n, base, SegSrcGlobal{&g, &b, &w, a});
       }
       continue;
     }
@@ -4092,8 +4139,11 @@ __global__ __launch_bounds__(TB, (PT <= 128 ? 4 : 2)) void k_segments(DevGraph g
     SEGP_MARK(2)
     if (nt > TR) {
       if (lane == 0) {
-        if (spill) spill[atomicAdd(spill_n, 1)] = t;
-        else segments_trace<true>(g, w, o, t, n, base, SegSrcGlobal{&g, &b, &w, a});
+        if (spill) {
+          tier_wake<TIER_SEG_LARGE>(w);
+          spill[atomicAdd(spill_n, 1)] = t;
+        } else
+          segments_trace<true>(g, w, o, t, n, base, SegSrcGlobal{&g, &b, &w, a});
       }
       wave_sync();
       continue;
@@ -5795,14 +5845,15 @@ constexpr int WIDE_GRID = OTM_WIDE_GRID;
   do {                   \
     mk.begin(k, s);      \
     launch;              \
+    mk.count();          \
     mk.end(k, s);        \
   } while (0)
 
-void launch_columns(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
-                    const Marks& mk) {
-  if (w.ord.tile_cnt) (void)hipMemsetAsync(w.ord.tile_cnt, 0, ORDER_TILES * 4, s);
+void launch_columns(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, int64_t* seg_base,
+                    hipStream_t s, const Marks& mk) {
+  // (the tile counts are zero: k_order_plan left them so)
   TIMED(KN_COLUMNS, hipLaunchKernelGGL(k_columns, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, g,
-                                       b, p, w));
+                                       b, p, w, seg_base));
 }
 // grid for a kernel over the spatial order: a multiple of ORDER_GROUPS, with
 // 25 % headroom per group over an even split
@@ -5821,6 +5872,7 @@ void launch_order(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk)
   hipLaunchKernelGGL(k_order_plan, dim3(1), dim3(1024), 0, s, w.ord.tile_cnt, w.ord.cursor, w.ord.grp);
   hipLaunchKernelGGL(k_order_scatter, dim3(grid_for(b.n_points, 256, 8192)), dim3(256), 0, s, b, w, w.ord.tile,
                      w.ord.cursor, w.ord.item);
+  mk.count(2);
   mk.end(KN_ORDER, s);
 }
 
@@ -5847,9 +5899,14 @@ void launch_candidates(const DevGraph& g, const DevBatch& b, const DevParams& p,
 #ifndef OTM_CAND_WAVE_GRID
 #define OTM_CAND_WAVE_GRID 4096
 #endif
-  if (from < RESUME_CAND_BIG)
+  if (from < RESUME_CAND_BIG) {
     hipLaunchKernelGGL(k_candidates<false>, dim3(OTM_CAND_WAVE_GRID), dim3(TB), 0, s, g, b, p, w);
-  hipLaunchKernelGGL(k_candidates<true>, dim3(CAND_BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
+    mk.count();
+  }
+  if (!(w.dormant & TIER_CAND_BIG)) {  // (on demand: kernels.h TierGroup)
+    hipLaunchKernelGGL(k_candidates<true>, dim3(CAND_BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
+    mk.count();
+  }
   mk.end(KN_CAND_WAVE, s);
 }
 void launch_links(const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s, const Marks& mk) {
@@ -5877,9 +5934,9 @@ void launch_expand_compact(const int64_t* trace_off, const int64_t* tbase, const
   hipLaunchKernelGGL(k_expand_compact, dim3(grid_for(((int64_t)n_traces + 3) / 4, 1, 1 << 20)), dim3(256), 0, s,
                      trace_off, tbase, dt, acc16, time, acc, n_traces);
 }
-void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, BatchStatus* out,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, s, abort, ttotal, counters, out);
+void launch_status(const int32_t* abort, const int64_t* ttotal, const int32_t* counters, const int32_t* snap,
+                   BatchStatus* out, BatchStatus* host, hipStream_t s) {
+  hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, s, abort, ttotal, counters, snap, out, host);
 }
 void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
                         const Marks& mk, int sub, int from) {
@@ -5887,6 +5944,7 @@ void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p
     // the tiers below the huge one kept their matrices: the huge tier alone
     mk.begin(KN_TRANS_GLOBAL, s);
     hipLaunchKernelGGL(k_transitions<2>, dim3(HUGE_SLOTS), dim3(TB), 0, s, g, b, p, w);
+    mk.count();
     mk.end(KN_TRANS_GLOBAL, s);
     return;
   }
@@ -5903,13 +5961,18 @@ void launch_transitions(const DevGraph& g, const DevBatch& b, const DevParams& p
     TIMED(KN_TRANS_WIDE, hipLaunchKernelGGL((k_trans_sub<16, true>), dim3(WIDE_GRID), dim3(TB), 0, s, g, b, p, w));
   } else {
     TIMED(KN_TRANS_INDEX, hipLaunchKernelGGL((k_trans_sub<16, false>), dim3(grid), dim3(TB), 0, s, g, b, p, w));
-    mk.begin(KN_TRANS_WIDE, s);
-    mk.end(KN_TRANS_WIDE, s);
+    mk.skip(KN_TRANS_WIDE, s);
+  }
+  if (w.dormant & TIER_TRANS_ONLINE) {  // (on demand: kernels.h TierGroup)
+    mk.skip(KN_TRANS_WAVE, s);
+    mk.skip(KN_TRANS_GLOBAL, s);
+    return;
   }
   TIMED(KN_TRANS_WAVE, hipLaunchKernelGGL(k_transitions<0>, dim3(SPILL_GRID), dim3(TB), 0, s, g, b, p, w));
   mk.begin(KN_TRANS_GLOBAL, s);
   hipLaunchKernelGGL(k_transitions<1>, dim3(BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
   hipLaunchKernelGGL(k_transitions<2>, dim3(HUGE_SLOTS), dim3(TB), 0, s, g, b, p, w);
+  mk.count(2);
   mk.end(KN_TRANS_GLOBAL, s);
 }
 void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& mk) {
@@ -5935,6 +5998,7 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   // what a form cannot take goes down a list to the next one (kernels.h: both
   // lists are free between the transition and route stages, K1 zeroes the counts)
   const SpillRef to_16 = spill_of<CTR_VIT_16>(w), to_wave = spill_of<CTR_VIT_WAVE>(w);
+  const bool lists = !(w.dormant & TIER_VIT_LISTS);  // the passes over those lists are launched
   if (form == 4) {
     // the row form (k_viterbi_row: four traces per wave) over every trace;
     // what it cannot take (more than VR_PTS points, a column wider than 16
@@ -5951,10 +6015,14 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
     mk.begin(KN_VITERBI, s);
     hipLaunchKernelGGL(k_viterbi_row, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
                        to_wave.list, to_wave.count, win, fast, 1);
+    mk.count();
     // (sized for every trace, as a batch of long traces needs: a block whose
-    // list entries ran out exits at once)
-    hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
-                       (const int32_t*)to_wave.list, (const int32_t*)to_wave.count, 0);
+    // list entries ran out exits at once; on demand: kernels.h TierGroup)
+    if (lists) {
+      hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces, 1, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
+                         (const int32_t*)to_wave.list, (const int32_t*)to_wave.count, 0);
+      mk.count();
+    }
     mk.end(KN_VITERBI, s);
     return;
   }
@@ -5974,15 +6042,23 @@ void launch_viterbi(const DevBatch& b, DevWork& w, hipStream_t s, const Marks& m
   if (form == 16) {
     hipLaunchKernelGGL(k_viterbi_g<16>, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
                        (const int32_t*)nullptr, (const int32_t*)nullptr, l16, n16, 1);
+    mk.count();
   } else {
     hipLaunchKernelGGL(k_viterbi_g<8>, dim3(grid_for(b.n_traces, TB / 8, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
                        (const int32_t*)nullptr, (const int32_t*)nullptr, l8, n8, 1);
+    mk.count();
     // (sized for every trace: a block whose list entries ran out exits at once)
-    hipLaunchKernelGGL(k_viterbi_g<16>, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
-                       (const int32_t*)l8, (const int32_t*)n8, l16, n16, 0);
+    if (lists) {
+      hipLaunchKernelGGL(k_viterbi_g<16>, dim3(grid_for(b.n_traces, TB / 16, WAVE_GRID_CAP)), dim3(TB), 0, s, b, w,
+                         (const int32_t*)l8, (const int32_t*)n8, l16, n16, 0);
+      mk.count();
+    }
   }
-  hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces / 64 + 1, 1, 1024)), dim3(TB), 0, s, b, w,
-                     (const int32_t*)l16, (const int32_t*)n16, 0);
+  if (lists) {
+    hipLaunchKernelGGL(k_viterbi, dim3(grid_for(b.n_traces / 64 + 1, 1, 1024)), dim3(TB), 0, s, b, w,
+                       (const int32_t*)l16, (const int32_t*)n16, 0);
+    mk.count();
+  }
   mk.end(KN_VITERBI, s);
 }
 void launch_route(const DevGraph& g, const DevBatch& b, const DevParams& p, DevWork& w, hipStream_t s,
@@ -5990,15 +6066,22 @@ void launch_route(const DevGraph& g, const DevBatch& b, const DevParams& p, DevW
   if (from >= RESUME_ROUTE_HUGE) {
     mk.begin(KN_ROUTE_GLOBAL, s);
     hipLaunchKernelGGL(k_route<2>, dim3(HUGE_SLOTS), dim3(TB), 0, s, g, b, p, w);
+    mk.count();
     mk.end(KN_ROUTE_GLOBAL, s);
     return;
   }
   TIMED(KN_ROUTE_INDEX, hipLaunchKernelGGL(k_route_index, dim3(order_grid(b.n_points, 256, 1 << 30)), dim3(256), 0,
                                            s, g, b, p, w));
+  if (w.dormant & TIER_ROUTE_ONLINE) {  // (on demand: kernels.h TierGroup)
+    mk.skip(KN_ROUTE_WAVE, s);
+    mk.skip(KN_ROUTE_GLOBAL, s);
+    return;
+  }
   TIMED(KN_ROUTE_WAVE, hipLaunchKernelGGL(k_route<0>, dim3(SPILL_GRID), dim3(TB), 0, s, g, b, p, w));
   mk.begin(KN_ROUTE_GLOBAL, s);
   hipLaunchKernelGGL(k_route<1>, dim3(BIG_SLOTS), dim3(TB), 0, s, g, b, p, w);
   hipLaunchKernelGGL(k_route<2>, dim3(HUGE_SLOTS), dim3(TB), 0, s, g, b, p, w);
+  mk.count(2);
   mk.end(KN_ROUTE_GLOBAL, s);
 }
 void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o, hipStream_t s, const Marks& mk) {
@@ -6011,8 +6094,12 @@ void launch_segments(const DevGraph& g, const DevBatch& b, DevWork& w, DevOut& o
   mk.begin(KN_SEG_WRITE, s);
   hipLaunchKernelGGL((k_segments<SEGP_PTS_S, SEGP_TRAV_S>), grid, dim3(TB), 0, s, g, b, w, o, (const int32_t*)nullptr,
                      (const int32_t*)nullptr, lst, cnt);
-  hipLaunchKernelGGL((k_segments<SEGP_PTS, SEGP_TRAV>), dim3(grid_for(b.n_traces, 1, 2048)), dim3(TB), 0, s, g, b, w,
-                     o, (const int32_t*)lst, (const int32_t*)cnt, (int32_t*)nullptr, (int32_t*)nullptr);
+  mk.count();
+  if (!(w.dormant & TIER_SEG_LARGE)) {  // (on demand: kernels.h TierGroup)
+    hipLaunchKernelGGL((k_segments<SEGP_PTS, SEGP_TRAV>), dim3(grid_for(b.n_traces, 1, 2048)), dim3(TB), 0, s, g, b,
+                       w, o, (const int32_t*)lst, (const int32_t*)cnt, (int32_t*)nullptr, (int32_t*)nullptr);
+    mk.count();
+  }
   mk.end(KN_SEG_WRITE, s);
 }
 void launch_queue(const DevBatch& b, DevWork& w, DevOut& o, float kph, hipStream_t s) {

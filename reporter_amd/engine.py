@@ -646,6 +646,17 @@ class Engine(object):
         _check(lib().otm_get_spill_stats(self.h, C.byref(st)))
         return {n: getattr(st, n) for n, _ in _lib.SpillStats._fields_ if n != "pad"}
 
+    TIERS = {"cand_big": 1, "trans_online": 2, "route_online": 4, "vit_lists": 8, "seg_large": 16}
+
+    def tiers(self):
+        """Tiers on demand (otm_get_tiers): the on-demand launch groups this
+        context does not launch now, by name, and the stream dispatches of its
+        last batch's final attempt."""
+        mask, disp = C.c_int32(), C.c_int32()
+        _check(lib().otm_get_tiers(self.h, C.byref(mask), C.byref(disp)))
+        return {"dormant": {n for n, b in self.TIERS.items() if mask.value & b}, "mask": mask.value,
+                "dispatches": disp.value}
+
     _DEBUG = {"ncand": (0, np.int32), "cand_edge": (1, np.int32), "cand_off": (2, np.float32),
               "cand_emis": (3, np.float32), "trans_off": (4, np.int64), "trans": (5, np.float32),
               "state": (6, np.int32), "col_prev": (7, np.int32), "route_dist": (8, np.float32),
